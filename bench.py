@@ -8,7 +8,19 @@ argmax), replayed as one hipGraph.  Inputs and weights are resident in HBM befor
 region; weights are deterministic synthetic values of the 3B architecture (no checkpoint is
 available offline).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: engine + synthetic weights, one prefill (it
+fills the KV cache and picks the first token), W warmup steps, the K timed steps, then the result line
+(metric / value / unit / ms_per_step / dtype / config / decode_step_hbm).  --full adds every other leg to
+the same line: the timed prefill and its vision / LM split, the prefill GEMM and decode GEMV rooflines,
+preprocessing, configs[1] at 256 tokens, configs[2] (no KV cache), configs[3] (8 images per GPU), the 448 px
+prefill, the drop-in module API, top-p sampling and the CPU baselines (each with its own --no-* switch).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step returned to its caller:
+DIR/logits.npy (float32, this rank's (B, V) logits, at most 64 MB: the first rows that fit) and
+DIR/next_ids.npy (float64, the greedy token of every image of the job, rank order).  Weights, images and
+prompt are seeded, so two runs with the same arguments read identical inputs.
 
 N > 1 (BASELINE.json configs[3]: images sharded 8 per GPU): one process per GPU.  Launched by
 torchrun (WORLD_SIZE set) it runs as that rank; started directly with --gpus N > 1 it re-launches
@@ -17,7 +29,7 @@ exits with the child's status.  Each rank is an independent replica; the weights
 rank 0 and RCCL-broadcast through libpgmi's C ABI (pgmi_broadcast_weights); --batch defaults to 8
 images per GPU, and value = tokens of all ranks / the max-over-ranks timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it also holds
   roofline      the dominant decode kernel (fused RMSNorm + gate/up GEMV + GeGLU), timed with
                 HIP events on its own stream, algorithmic bytes per launch / average duration
   cpu_baseline  the decode step on this host's cores: a torch bf16 port (oracle/torch_cpu.py), with the
@@ -53,6 +65,12 @@ def parse():
                     help="images (sequences) per GPU (default 1 on one GPU -- configs[1]; 8 with N > 1 -- configs[3])")
     ap.add_argument("--image-size", type=int, default=224)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (logits.npy float32, next_ids.npy float64) into DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline decode figure (prefill timing, rooflines, the other "
+                         "BASELINE configs, the drop-in API, sampling, CPU baselines); the --no-* switches and the "
+                         "iteration counts below act only with --full")
     ap.add_argument("--prefill-iters", type=int, default=20)
     ap.add_argument("--kernel-iters", type=int, default=90)
     ap.add_argument("--cpu-steps", type=int, default=12)
@@ -587,6 +605,20 @@ def time_ablation(m, ids0, px, tokens, warmup=32):
                          "(pgmi_decode_embeds); steady state after 32 tokens as the harness reports it"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, logits, gathered):
+    """--dump-outputs: the last timed step's outputs as its caller holds them -- this rank's logits (B, V)
+    fp32 (the first rows that fit DUMP_MAX_BYTES) and the greedy token of every image of the job."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    ids = gathered.reshape(-1).cpu().numpy().astype(np.float64)
+    rows = max(1, min(logits.shape[0], (DUMP_MAX_BYTES - ids.nbytes) // (logits.shape[1] * 4)))
+    np.save(os.path.join(path, "logits.npy"), logits[:rows].float().cpu().numpy())
+    np.save(os.path.join(path, "next_ids.npy"), ids)
+
+
 def rank_plan(a, world, rank):
     """Images per rank and this rank's contiguous shard [lo, hi) of the job's images (configs[3]:
     64 images = 8 per GPU x 8; pgmi.dist.shard_range)."""
@@ -705,9 +737,12 @@ def main():
     pos = torch.arange(L).expand(B, L)
     kv = eng.new_kv(B, kv_cap)
 
-    prefill_ms, vision_ms, lm_ms, lg = time_prefill(eng, px, ids, pos, kv, a.prefill_iters)
-    prefill_gemms = with_insitu(gemm_roofline(eng, B * L), *gemm_insitu(eng, px, ids, pos, kv))
-    pre_ms = time_preprocess(eng, dev, a.image_size)
+    if a.full:
+        prefill_ms, vision_ms, lm_ms, lg = time_prefill(eng, px, ids, pos, kv, a.prefill_iters)
+        prefill_gemms = with_insitu(gemm_roofline(eng, B * L), *gemm_insitu(eng, px, ids, pos, kv))
+        pre_ms = time_preprocess(eng, dev, a.image_size)
+    else:  # one prefill: the KV cache of the prompt and the first token
+        lg = eng.lm_forward(kv, 0, pos, ids=ids, image_feats=eng.project(eng.vision(px)), logits_rows=2)
 
     # ---- decode: warmup, then exactly K timed steps (graph replay, device-side argmax)
     first = eng.argmax(lg[:, 0])
@@ -734,6 +769,57 @@ def main():
     tok_s = world * B * a.steps / elapsed
     T_mid = L + a.warmup + a.steps // 2
     step_bytes = DECODE_WEIGHT_BYTES + B * KV_BYTES_PER_TOKEN * T_mid
+
+    out = None
+    if rank == 0:
+        if world > 1 or B > 1:
+            workload = (f"configs[3]: paligemma-3b-pt-{a.image_size}, {B} synthetic images per GPU x {world} GPU(s) "
+                        f"(global batch {B * world}), lock-step greedy KV-cached decode after a {n_img}-image-token "
+                        f"+ 32-text-token prefill")
+        else:
+            workload = (f"configs[1]: paligemma-3b-pt-{a.image_size} greedy KV-cached decode, batch 1, after a "
+                        f"{n_img}-image-token + 32-text-token prefill")
+        out = {
+            "metric": "decode tokens/sec per GPU + prefill ms (224px img + 32-tok prompt), PaliGemma-3B",
+            "value": round(tok_s, 3),
+            "unit": "tokens/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "vs_baseline_note": "BASELINE.md publishes no number for this hardware/dtype; its only decode figure is "
+                                "10.17 tok/s per GPU (RTX 2060, fp16, KV cache, 256 tokens)",
+            "per_gpu_tok_s": round(tok_s / world, 3),
+            # N > 1 runs configs[3] (8 images per GPU), N = 1 configs[1] (batch 1): the like-for-like single-GPU
+            # figure for a scaling ratio of the N > 1 lines is the N = 1 line's config4_images_per_gpu leg
+            "scaling_reference": ("config4_images_per_gpu.decode_tok_s of the N = 1 line (the same per-GPU work: "
+                                  "8 images)" if world > 1 else None),
+            "dtype": "bf16",
+            "data": "synthetic (deterministic random-init PaliGemma-3B weights, seeded random 224x224 images, "
+                    "synthetic 32-token prompt)",
+            "config": {"workload": workload, "batch_per_gpu": B, "global_batch": B * world, "prompt_len": L,
+                       "images_gathered": int(gathered.shape[0]),
+                       "decode_tokens_timed": a.steps, "parallelism": f"replicas x{world} (weights RCCL-broadcast)",
+                       "hipgraph": graph, "steps_per_graph_launch": chunk},
+            "decode_step_hbm": {"algorithmic_bytes": step_bytes,
+                                "achieved_GBs": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
+                                "frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+        }
+        if bcast_ms is not None:
+            out["weight_broadcast_ms"] = round(bcast_ms, 2)
+            out["weight_broadcast_bytes"] = slab_bytes
+            out["weight_broadcast_GBs"] = round(slab_bytes / (bcast_ms * 1e-3) / 1e9, 1)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, logits, gathered)
+    if not a.full:  # a plain run ends here: the headline figure alone
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- dominant kernel: fused RMSNorm + gate/up GEMV + GeGLU (kernel id 2), HIP events on
     # the stream it is launched on; cycling the 18 layers streams 2.4 GB (>> 256 MiB MALL)
@@ -801,44 +887,10 @@ def main():
         cpu = cpu_baseline(OW.full_config(a.image_size), a.seed, L, a.cpu_steps)
 
     if rank == 0:
-        if world > 1 or B > 1:
-            workload = (f"configs[3]: paligemma-3b-pt-{a.image_size}, {B} synthetic images per GPU x {world} GPU(s) "
-                        f"(global batch {B * world}), lock-step greedy KV-cached decode after a {n_img}-image-token "
-                        f"+ 32-text-token prefill")
-        else:
-            workload = (f"configs[1]: paligemma-3b-pt-{a.image_size} greedy KV-cached decode, batch 1, after a "
-                        f"{n_img}-image-token + 32-text-token prefill")
-        out = {
-            "metric": "decode tokens/sec per GPU + prefill ms (224px img + 32-tok prompt), PaliGemma-3B",
-            "value": round(tok_s, 3),
-            "unit": "tokens/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "vs_baseline_note": "BASELINE.md publishes no number for this hardware/dtype; its only decode figure is "
-                                "10.17 tok/s per GPU (RTX 2060, fp16, KV cache, 256 tokens)",
-            "per_gpu_tok_s": round(tok_s / world, 3),
-            # N > 1 runs configs[3] (8 images per GPU), N = 1 configs[1] (batch 1): the like-for-like single-GPU
-            # figure for a scaling ratio of the N > 1 lines is the N = 1 line's config4_images_per_gpu leg
-            "scaling_reference": ("config4_images_per_gpu.decode_tok_s of the N = 1 line (the same per-GPU work: "
-                                  "8 images)" if world > 1 else None),
-            "dtype": "bf16",
-            "data": "synthetic (deterministic random-init PaliGemma-3B weights, seeded random 224x224 images, "
-                    "synthetic 32-token prompt)",
-            "config": {"workload": workload, "batch_per_gpu": B, "global_batch": B * world, "prompt_len": L,
-                       "images_gathered": int(gathered.shape[0]),
-                       "decode_tokens_timed": a.steps, "parallelism": f"replicas x{world} (weights RCCL-broadcast)",
-                       "hipgraph": graph, "steps_per_graph_launch": chunk},
+        out.update({
             "prefill_ms": round(prefill_ms, 3),
             "prefill_vision_ms": round(vision_ms, 3),
             "prefill_lm_ms": round(lm_ms, 3),
-            "decode_step_hbm": {"algorithmic_bytes": step_bytes,
-                                "achieved_GBs": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-                                "frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
             "roofline": {"kernel": f"k_gemv<{B},...,GV_GEGLU> (RMSNorm + gate/up GEMV + GeGLU)",
                          "bound": "hbm", "achieved": round(k_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(k_gbs / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
@@ -853,11 +905,7 @@ def main():
             "dropin_api": api,
             "sample_top_p_us": sample_us,
             "cpu_baseline": cpu,
-        }
-        if bcast_ms is not None:
-            out["weight_broadcast_ms"] = round(bcast_ms, 2)
-            out["weight_broadcast_bytes"] = slab_bytes
-            out["weight_broadcast_GBs"] = round(slab_bytes / (bcast_ms * 1e-3) / 1e9, 1)
+        })
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -288,3 +288,28 @@ def test_bench_decode_chunking():
     bench.run_decode(e, "cur", None, 288, 5, 8, 4, None, True)
     assert e.calls == [("steps", 288, 289, 2), ("steps", 290, 291, 2), ("one", 292, 293, 1),
                        ("steps", 293, 294, 4), ("steps", 297, 298, 4)]
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's logits as float32 and every image's token as float64 (ids
+    below 2^53 are exact), whole while they fit DUMP_MAX_BYTES and the first rows that fit beyond it; --full
+    is off unless asked for."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.dump_outputs == str(tmp_path) and a.full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True and bench.parse().dump_outputs is None
+    logits = torch.arange(3 * 7, dtype=torch.float32).reshape(3, 7) / 3
+    toks = torch.tensor([[257215], [5], [0], [9]])  # the job's images: this rank's 3 rows and another rank's
+    bench.dump_outputs(str(tmp_path / "d"), logits, toks)
+    lg, ids = np.load(tmp_path / "d" / "logits.npy"), np.load(tmp_path / "d" / "next_ids.npy")
+    assert lg.dtype == np.float32 and np.array_equal(lg, logits.numpy())
+    assert ids.dtype == np.float64 and ids.tolist() == [257215.0, 5.0, 0.0, 9.0]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 7 * 4 + 4 * 8)
+    bench.dump_outputs(str(tmp_path / "e"), logits, toks)
+    assert np.array_equal(np.load(tmp_path / "e" / "logits.npy"), logits[:2].numpy())

@@ -6,7 +6,7 @@ set -e
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$1
 shift
-BENCH_ARGS=${@:-"--no-448 --no-extra --no-api --no-cpu-baseline --prefill-iters 3 --steps 64"}
+BENCH_ARGS=${@:-"--full --no-448 --no-extra --no-api --no-cpu-baseline --prefill-iters 3 --steps 64"}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for v in base new; do

@@ -8,7 +8,7 @@ mkdir -p $R/gpurun_out/b8env
 N=$1; shift
 for i in $(seq 1 $N); do
   for E in "" "$@"; do
-    env $E timeout -k 10 300 python $R/bench.py --no-448 --no-api --no-cpu-baseline --prefill-iters 3 --steps 32 \
+    env $E timeout -k 10 300 python $R/bench.py --full --no-448 --no-api --no-cpu-baseline --prefill-iters 3 --steps 32 \
       --nokv-tokens 2 > $R/gpurun_out/b8env/b.json 2> /dev/null
     echo "[$E] $(python3 -c 'import sys,json; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c=d["config4_images_per_gpu"]; print(d["value"], c["ms_per_step"], c["decode_tok_s"])' $R/gpurun_out/b8env/b.json)"
   done

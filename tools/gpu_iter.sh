@@ -9,7 +9,7 @@ mkdir -p $OUT
 if [ -n "$2" ] && [ "$2" != "all" ]; then K="-k $2"; else K=""; fi
 timeout -k 10 700 python -u -m pytest $R/tests -m gpu -x -v --timeout 300 --timeout-method thread $K > $OUT/tests.log 2>&1
 echo tests done
-timeout -k 10 400 python3 -u $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 -u $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo bench done
 if [ "$3" = "list" ]; then
   cd /tmp && export TMPDIR=/tmp

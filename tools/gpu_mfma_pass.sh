@@ -11,7 +11,7 @@ mkdir -p $OUT
 HB=$!
 trap "kill $HB" EXIT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 16 --warmup 4 --no-cpu-baseline --no-api --prefill-iters 3 --kernel-iters 18 --nokv-tokens 2"
+ARGS="--full --steps 16 --warmup 4 --no-cpu-baseline --no-api --prefill-iters 3 --kernel-iters 18 --nokv-tokens 2"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
     python3 $R/bench.py $ARGS > $OUT/trace.log 2>&1
 echo trace done

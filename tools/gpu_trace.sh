@@ -9,6 +9,6 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-    python3 $R/bench.py --steps 64 --warmup 8 --no-cpu-baseline --prefill-iters 5 --no-448 --no-extra --no-api "$@" \
+    python3 $R/bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --prefill-iters 5 --no-448 --no-extra --no-api "$@" \
     > $OUT/bench_trace.log 2>&1
 echo done
