@@ -143,6 +143,36 @@ int pgmi_decode(pgmi_ctx* ctx, const int64_t* ids, int B, void* kv, int kv_batch
  * NULL) records every step's argmax.  Each step is pgmi_decode's step, kernel for kernel. */
 int pgmi_decode_steps(pgmi_ctx* ctx, int64_t* ids, int B, void* kv, int kv_batch, int kv_max, int kv_len,
                       int position, int n_steps, float* logits, int64_t* tokens, int use_graph, void* stream);
+/* ---- ragged batches: every row with its own prompt length ------------------------------------
+ * The reference refuses padded batches (modeling_gemma.py:559) and its drop-in modules keep that;
+ * these two entries are the engine's own batched driver for prompts of different lengths.  Each row
+ * computes what it would compute alone (a batch of one, unpadded).
+ *
+ * pgmi_lm_forward with per-row lengths: ids is (B, L) right-padded, lens (HOST int32 [B],
+ * 1 <= lens[b] <= L) the rows' token counts.  Token j < lens[b] has rotary position positions[b][j]
+ * (= j for an inference.py:55-63 prefill) and attends keys [0, kv_start + lens[b]) of its own row,
+ * non-causal: the zero mask of modeling_gemma.py:516-535 restricted to the row's real tokens.  Pad
+ * slots j >= lens[b] are never looked up (any id is legal there; they enter as zero rows), are never
+ * attended by real tokens and never reach a returned value; what is computed for them, and their
+ * K/V rows, is unspecified but finite.  logits_rows 1 and 2 return row b's logits at token
+ * lens[b] - 1 (2 runs as 1); logits_rows 0 returns all L rows, pad rows unspecified.  embeds must
+ * be NULL.  PGMI_E_ARG: a length outside [1, L], B over capacity, null arrays. */
+int pgmi_lm_forward_ragged(pgmi_ctx* ctx, const int64_t* ids, const void* image_feats, int n_img_rows,
+                           const void* embeds, int B, int L, const int64_t* positions, const int32_t* lens, void* kv,
+                           int kv_batch, int kv_max, int kv_start, float* logits, int logits_rows, void* stream);
+/* n_steps >= 1 decode steps (inference.py:55-78 loop body) for B rows of different lengths: kv_lens
+ * and positions are HOST int32 [B].  At step t row b writes K/V at row kv_lens[b] + t, attends keys
+ * [0, kv_lens[b] + t] and uses rotary position positions[b] + t (after a ragged prefill
+ * positions[b] = lens[b] + 1: attention_mask.cumsum(-1)[:, -1] of modeling_gemma.py:526 for that row
+ * alone).  The per-row state lives on the device and is advanced by the step's last kernel, so a call
+ * that continues the previous one sets nothing, and graph replay, in-place feedback (next_ids == ids)
+ * and the token record work as pgmi_decode / pgmi_decode_steps: logits holds the last step's, next_ids
+ * (required when n_steps > 1) every step's argmax in turn, tokens (may be NULL) [n_steps][B].
+ * Nothing at or past a row's own length is read.  PGMI_E_ARG: a row with
+ * kv_lens[b] + n_steps > kv_max, B over capacity, null arrays. */
+int pgmi_decode_ragged(pgmi_ctx* ctx, const int64_t* ids, int B, void* kv, int kv_batch, int kv_max,
+                       const int32_t* kv_lens, const int32_t* positions, int n_steps, float* logits, int64_t* next_ids,
+                       int64_t* tokens, int use_graph, void* stream);
 /* The same decode step with already-merged input rows instead of token ids: embeds (device bf16
  * [B][hidden]) is the output of a caller's _merge_input_ids_with_image_features for a q_len == 1
  * step (the ablation harness monkey-patches the merge, ablation_study_fixed.py:99-142,335-337,

@@ -30,6 +30,8 @@ __device__ __forceinline__ short8 frag256(const uint16_t* rowp, int kk, int lane
     return __builtin_bit_cast(short8, ldg16(rowp + k));
 }
 
+// st: batch row b's own step record (the caller indexes the array: st + b * st_stride), so on the ragged
+// step a chunk at or past this row's chunk count returns early while a longer neighbour's runs
 __device__ __forceinline__ void attn_decode_block(const AttnArgs& a, const StepState* st, float* __restrict__ part,
                                                   int max_chunks, int chunk, int kvh, int b, unsigned char* lds) {
     const int kv_len = st->kv_len;

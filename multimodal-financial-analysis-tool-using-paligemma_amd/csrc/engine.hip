@@ -65,10 +65,11 @@ struct GraphKey {
     int masked;          // 0: no mask (a zero word), 1: staged bf16 mask (sum rounded), 2: staged fp32 mask
     int n_steps;         // decode steps captured back to back (pgmi_decode_steps; 1 otherwise)
     int64_t* tokens;     // their per-step token record ([n_steps][B], may be null)
+    bool ragged;         // per-row step records (pgmi_decode_ragged): never aliases a lock-step graph
     bool operator<(const GraphKey& o) const {
-        return std::tie(B, kv, kv_batch, kv_max, logits, next, ids, emb, masked, n_steps, tokens) <
+        return std::tie(B, kv, kv_batch, kv_max, logits, next, ids, emb, masked, n_steps, tokens, ragged) <
                std::tie(o.B, o.kv, o.kv_batch, o.kv_max, o.logits, o.next, o.ids, o.emb, o.masked, o.n_steps,
-                        o.tokens);
+                        o.tokens, o.ragged);
     }
 };
 
@@ -116,6 +117,8 @@ struct pgmi_ctx {
     int max_chunks;
     StepState* step;
     StepState* pstep;  // the generate-loop prefill's last-row attention (flash-decoding over the prompt's keys)
+    StepState* rstep;  // the ragged step's records, one per batch row ([max_batch], pgmi_decode_ragged)
+    int* d_rlens;      // ragged prefill: [0, 8) each row's token count, [8, 16) its attended key count
     int64_t* d_ids;
     uint16_t* d_emb;             // staged input rows of pgmi_decode_embeds ([max_batch][hidden] bf16)
     float* d_mask;               // staged additive decode mask ([max_batch][max_kv] fp32, pgmi_decode_embeds_dev)
@@ -132,6 +135,10 @@ struct pgmi_ctx {
     // device step state as the last enqueued per-phase decode step leaves it (advanced in-graph)
     bool step_known = false;
     int step_kv = 0, step_pos = 0;
+    // the same for the ragged step's per-row records (rows [0, rstep_B))
+    bool rstep_known = false;
+    int rstep_B = 0;
+    int rstep_kv[8] = {0}, rstep_pos[8] = {0};
     std::map<std::vector<intptr_t>, GraphEntry> pgraphs;
     // in-situ timing probe of the prefill MLP GEMMs (pgmi_prefill_probe): events around layer i's gate|up
     // GEMM (ev[4i], ev[4i+1]) and down GEMM (ev[4i+2], ev[4i+3]) of eager forwards
@@ -617,6 +624,8 @@ int pgmi_prepare(pgmi_ctx* x) {
         if ((rc = dalloc_t(x, &x->pidx, (size_t)B * gemv_logits_blocks()))) return rc;
         if ((rc = dalloc_t(x, &x->step, 1))) return rc;
         if ((rc = dalloc_t(x, &x->pstep, 1))) return rc;
+        if ((rc = dalloc_t(x, &x->rstep, 8))) return rc;
+        if ((rc = dalloc_t(x, &x->d_rlens, 16))) return rc;
         if ((rc = dalloc_t(x, &x->amax_v, (size_t)argmax_scratch_parts()))) return rc;
         if ((rc = dalloc_t(x, &x->amax_i, (size_t)argmax_scratch_parts()))) return rc;
         if ((rc = dalloc_t(x, &x->d_ids, (size_t)B))) return rc;
@@ -794,11 +803,30 @@ int pgmi_embed(pgmi_ctx* x, const int64_t* ids, int rows, void* out, void* strea
 
 static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
                    const void* embeds, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
-                   int logits_rows);
+                   int logits_rows, bool ragged);
+
+static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows, const void* embeds,
+                      int B, int L, const int64_t* positions, const int32_t* lens, bool ragged, void* kv, int kv_batch,
+                      int kv_max, int kv_start, float* logits, int logits_rows, void* stream);
 
 int pgmi_lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows, const void* embeds,
                     int B, int L, const int64_t* positions, void* kv, int kv_batch, int kv_max, int kv_start,
                     float* logits, int logits_rows, void* stream) {
+    return lm_forward(x, ids, image_feats, n_img_rows, embeds, B, L, positions, nullptr, false, kv, kv_batch, kv_max,
+                      kv_start, logits, logits_rows, stream);
+}
+
+int pgmi_lm_forward_ragged(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows,
+                           const void* embeds, int B, int L, const int64_t* positions, const int32_t* lens, void* kv,
+                           int kv_batch, int kv_max, int kv_start, float* logits, int logits_rows, void* stream) {
+    if (!lens) return fail(PGMI_E_ARG, "null argument");
+    return lm_forward(x, ids, image_feats, n_img_rows, embeds, B, L, positions, lens, true, kv, kv_batch, kv_max,
+                      kv_start, logits, logits_rows, stream);
+}
+
+static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows, const void* embeds,
+                      int B, int L, const int64_t* positions, const int32_t* lens, bool ragged, void* kv, int kv_batch,
+                      int kv_max, int kv_start, float* logits, int logits_rows, void* stream) {
     int rc;
     if ((rc = ensure_prepared(x))) return rc;
     const pgmi_config& c = x->c;
@@ -807,16 +835,30 @@ int pgmi_lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, in
     if (kv_start < 0 || kv_start + L > kv_max) return fail(PGMI_E_ARG, "KV cache capacity exceeded");
     if (!positions || !kv || !logits || (!embeds && !ids)) return fail(PGMI_E_ARG, "null argument");
     if (logits_rows < 0 || logits_rows > 2) return fail(PGMI_E_ARG, "logits_rows must be 0, 1 or 2");
+    if (ragged) {
+        // per-row token counts -> the context's device buffer, outside any graph (a replay reads this call's)
+        if (embeds || !ids) return fail(PGMI_E_ARG, "ragged prefill takes token ids (pad slots enter as zero rows)");
+        RowInts rl{}, rk{};
+        for (int b = 0; b < B; ++b) {
+            if (lens[b] < 1 || lens[b] > L) return fail(PGMI_E_ARG, "lens[b] must be in [1, L]");
+            rl.v[b] = lens[b];
+            rk.v[b] = kv_start + lens[b];
+        }
+        set_row_ints((hipStream_t)stream, x->d_rlens, rl, rk, B);
+        LAUNCHCHK();
+        if (logits_rows == 2) logits_rows = 1;  // the last-row-only form is the lock-step prefill's
+    }
     // host positions -> device (outside any graph: a pageable host copy is not captured)
     HIPCHK(hipMemcpyAsync(x->dpos, positions, (size_t)B * L * sizeof(int64_t), hipMemcpyHostToDevice,
                           (hipStream_t)stream));
     // Tn is overwritten from here on: no row of it is valid until this call has succeeded
     x->tn_rows = 0;
     const std::vector<intptr_t> key{2, (intptr_t)ids, (intptr_t)image_feats, n_img_rows, (intptr_t)embeds, B, L,
-                                    (intptr_t)kv, kv_batch, kv_max, kv_start, (intptr_t)logits, logits_rows};
+                                    (intptr_t)kv, kv_batch, kv_max, kv_start, (intptr_t)logits, logits_rows,
+                                    (intptr_t)ragged};
     rc = run_graphed(x, (hipStream_t)stream, key, [&](hipStream_t st) {
         return lm_body(x, st, ids, image_feats, n_img_rows, embeds, B, L, kv, kv_batch, kv_max, kv_start, logits,
-                       logits_rows);
+                       logits_rows, ragged);
     });
     if (rc) return rc;
     x->tn_rows = logits_rows == 2 && L > 1 ? 0 : (long)B * L;
@@ -826,8 +868,11 @@ int pgmi_lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, in
 
 static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
                    const void* embeds, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
-                   int logits_rows) {
+                   int logits_rows, bool ragged) {
     const pgmi_config& c = x->c;
+    // ragged: row b holds lens[b] tokens (d_rlens, set outside the graph), the rest of its L slots is padding
+    const int* rlens = ragged ? x->d_rlens : nullptr;
+    const int* rkeys = ragged ? x->d_rlens + 8 : nullptr;
     const int H = c.t_hidden, R = B * L, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
     const int QKVN = (NH + 2 * NKV) * HD;
     const float eps = c.t_rms_eps;
@@ -838,7 +883,7 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
     } else {
         merge_embed(s, ids, B, L, E, H, reinterpret_cast<const uint16_t*>(image_feats), image_feats ? n_img_rows : 0,
                     c.image_token_index, c.pad_token_id, (float)std::sqrt((double)H), normalizer, nullptr,
-                    reinterpret_cast<int*>(x->dids_tmp), x->Hs);
+                    reinterpret_cast<int*>(x->dids_tmp), x->Hs, rlens);
     }
     const long kvd = (long)NKV * HD, kvb = (long)kv_max * kvd;
     uint16_t* kvp = reinterpret_cast<uint16_t*>(kv);
@@ -870,6 +915,7 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
         a.Lq = L; a.Lk = kv_start + L; a.G = NH / NKV; a.n_kv = NKV; a.B = B;
         a.scale = 1.0f / std::sqrt((float)HD);  // / math.sqrt(head_dim) (:266): exact power of two
         a.ws = x->ws; a.ws_floats = (long)(x->ws_bytes / sizeof(float));
+        a.klen = rkeys;  // ragged: row b's real tokens attend its own real keys only
         if (last_only && i + 1 == c.t_layers) {
             // logits_rows == 2, last layer: the K/V rows of every token are written above (the cache
             // the decode loop reads); the rest of the layer feeds only the final hidden state, and the
@@ -929,7 +975,9 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
         l.out_f32 = logits; l.ldo = c.t_vocab;
         gemm(s, x->Tn, H, E, H, R, c.t_vocab, H, EPI_F32, l, x->ws, x->ws_bytes);
     } else {
-        if (!last_only)
+        if (ragged)  // each row's last real token, lens[b] - 1
+            gather_last_rows(s, x->Hs, B, L, H, rlens, x->lastrows);
+        else if (!last_only)
             HIPCHK(hipMemcpy2DAsync(x->lastrows, (size_t)H * 2, x->Hs + (size_t)(L - 1) * H, (size_t)L * H * 2,
                                     (size_t)H * 2, B, hipMemcpyDeviceToDevice, s));
         int nparts = 0;
@@ -951,8 +999,11 @@ static bool mf_staged(const pgmi_ctx* x) { return x->mf_staged > 0; }
 
 static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, void* kv, int kv_batch, int kv_max,
                        int launch_keys, float* logits, int64_t* next_ids, const uint16_t* embeds = nullptr,
-                       int masked = 0, int64_t* hist = nullptr) {
+                       int masked = 0, int64_t* hist = nullptr, bool ragged = false) {
     const pgmi_config& c = x->c;
+    // the step record(s) the kernels read: one shared by every row, or (ragged) one per row
+    StepState* const st = ragged ? x->rstep : x->step;
+    const int sts = ragged ? 1 : 0, adv_n = ragged ? B : 1;
     const int H = c.t_hidden, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
     const float eps = c.t_rms_eps;
     const float normalizer = bf16_round_host(std::sqrt((float)H));
@@ -980,8 +1031,8 @@ static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, vo
         const uint16_t* Lf = x->mfw ? x->mfw + x->mfw_layer * i : nullptr;
         const size_t gu_n = (size_t)2 * c.t_intermediate * H, qkv_n = (size_t)(NH + 2 * NKV) * HD * H;
         gemv_qkv(s, B, NH, NKV, mf ? x->dHn : x->dH, mf ? nullptr : TL(x, i, "input_layernorm.weight"), eps,
-                 TL(x, i, "self_attn.q_proj.weight"), x->cosT, x->sinT, c.t_max_pos, x->step, x->dQ, Kc, Vc, kvb, x->ws,
-                 (fold && i == 0) ? &emb : nullptr, Lf ? Lf + gu_n : nullptr);
+                 TL(x, i, "self_attn.q_proj.weight"), x->cosT, x->sinT, c.t_max_pos, st, x->dQ, Kc, Vc, kvb, x->ws,
+                 (fold && i == 0) ? &emb : nullptr, Lf ? Lf + gu_n : nullptr, sts);
         AttnArgs a{};
         a.q = x->dQ; a.q_b_stride = (long)NH * HD; a.q_row_stride = NH * HD; a.q_head_stride = HD;
         a.k = Kc; a.k_b_stride = kvb; a.k_row_stride = (int)kvd; a.k_head_stride = HD;
@@ -993,9 +1044,10 @@ static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, vo
         } else {
             a.mask = x->d_zero; a.mask_b_stride = 0; a.mask_k_stride = 0; a.mask_round = 1;
         }
-        attention_decode(s, a, x->step, launch_keys, x->opart, x->max_chunks);
-        gemv_o_attn(s, B, NH, x->opart, x->max_chunks, x->step, TL(x, i, "self_attn.o_proj.weight"), H, x->dH,
-                    B >= gemv_mf_min_batch() ? x->dAO : nullptr, mf ? x->dSS : nullptr, Lf ? Lf + gu_n + qkv_n : nullptr);
+        attention_decode(s, a, st, launch_keys, x->opart, x->max_chunks, sts);
+        gemv_o_attn(s, B, NH, x->opart, x->max_chunks, st, TL(x, i, "self_attn.o_proj.weight"), H, x->dH,
+                    B >= gemv_mf_min_batch() ? x->dAO : nullptr, mf ? x->dSS : nullptr, Lf ? Lf + gu_n + qkv_n : nullptr,
+                    sts);
         if (mf) {
             // the post-attention RMSNorm: its sums of squares come from o_proj's epilogue (dSS), gate|up
             // normalises h on load (no k_rows_norm pass: B = 8 step -5 us per layer)
@@ -1015,8 +1067,8 @@ static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, vo
     // the step's last work also advances the device step state (pgmi_decode skips its host-side
     // set when the next call continues the sequence): lm_head's last workgroup, or argmax_finish
     if (!gemv_logits(s, B, x->dH, W(x, "language_model.model.norm.weight"), eps, E, c.t_vocab, logits, x->pmax,
-                     x->pidx, &nparts, x->lm_done, nx, x->step, hist))
-        argmax_finish(s, B, x->pmax, x->pidx, nparts, nx, x->step, hist);
+                     x->pidx, &nparts, x->lm_done, nx, st, hist, adv_n))
+        argmax_finish(s, B, x->pmax, x->pidx, nparts, nx, st, hist, adv_n);
     return 0;
 }
 
@@ -1111,13 +1163,26 @@ static int ensure_mf_image(pgmi_ctx* x, hipStream_t s) {
 
 static int decode_step(pgmi_ctx* x, const int64_t* ids, const void* embeds, int B, void* kv, int kv_batch, int kv_max,
                        int kv_len, int position, float* logits, int64_t* next_ids, int use_graph, void* stream,
-                       const DevStepIn* dev = nullptr, int n_steps = 1, int64_t* tokens = nullptr) {
+                       const DevStepIn* dev = nullptr, int n_steps = 1, int64_t* tokens = nullptr,
+                       const int32_t* r_kv = nullptr, const int32_t* r_pos = nullptr) {
     int rc;
+    // ragged (pgmi_decode_ragged): host arrays of each row's KV write row and rotary position; kv_len is
+    // then the largest row's (it sizes the eager launches' attention grid)
+    const bool ragged = r_kv != nullptr;
     if ((rc = ensure_prepared(x))) return rc;
     const pgmi_config& c = x->c;
     if (B < 1 || B > c.max_batch || B > kv_batch) return fail(PGMI_E_ARG, "batch exceeds capacity");
     if (n_steps < 1) return fail(PGMI_E_ARG, "n_steps must be >= 1");
     if (n_steps > 1 && (!ids || embeds || dev)) return fail(PGMI_E_ARG, "multi-step decode: token ids only");
+    if (ragged) {
+        if (!r_pos) return fail(PGMI_E_ARG, "null argument");
+        kv_len = 0;
+        for (int b = 0; b < B; ++b) {
+            if (r_kv[b] < 0 || (long)r_kv[b] + n_steps - 1 >= kv_max)
+                return fail(PGMI_E_ARG, "KV cache capacity exceeded (a row's kv_lens[b] + n_steps > kv_max)");
+            kv_len = std::max(kv_len, (int)r_kv[b]);
+        }
+    }
     if (kv_len < 0 || (long)kv_len + n_steps - 1 >= kv_max) return fail(PGMI_E_ARG, "KV cache capacity exceeded");
     if (kv_max > c.max_kv) return fail(PGMI_E_ARG, "kv_max exceeds config max_kv");
     if ((!ids && !embeds) || !kv || !logits) return fail(PGMI_E_ARG, "null argument");
@@ -1131,13 +1196,32 @@ static int decode_step(pgmi_ctx* x, const int64_t* ids, const void* embeds, int 
             stage_mask(s, dev->mask, dev->mask_dtype, B, dev->mask_b_stride, kv_len + 1, x->d_mask, c.max_kv);
             masked = dev->mask_dtype == PGMI_DTYPE_F32 ? 2 : 1;
         }
+    } else if (ragged) {
+        // the per-row records are set only when this call does not continue the previous ragged one
+        bool same = x->rstep_known && x->rstep_B == B;
+        for (int b = 0; same && b < B; ++b) same = x->rstep_kv[b] == r_kv[b] && x->rstep_pos[b] == r_pos[b];
+        if (!same) {
+            RowInts rk{}, rp{};
+            for (int b = 0; b < B; ++b) { rk.v[b] = r_kv[b]; rp.v[b] = r_pos[b]; }
+            set_step_rows(s, x->rstep, rk, rp, B);
+        }
     } else if (!x->step_known || x->step_kv != kv_len || x->step_pos != position) {
         set_step(s, x->step, kv_len, position);
     }
     // the step advances the device state itself (its last kernel); known only once this call has
-    // enqueued its steps successfully
-    x->step_known = false;
+    // enqueued its steps successfully (a ragged call leaves the lock-step record, and its mirror, alone)
+    if (ragged) x->rstep_known = false;
+    else x->step_known = false;
     auto advanced = [&]() {
+        if (ragged) {
+            x->rstep_known = true;
+            x->rstep_B = B;
+            for (int b = 0; b < B; ++b) {
+                x->rstep_kv[b] = r_kv[b] + n_steps;
+                x->rstep_pos[b] = r_pos[b] + n_steps;
+            }
+            return;
+        }
         x->step_known = dev == nullptr;
         x->step_kv = kv_len + n_steps;
         x->step_pos = position + n_steps;
@@ -1154,7 +1238,8 @@ static int decode_step(pgmi_ctx* x, const int64_t* ids, const void* embeds, int 
     auto body = [&](hipStream_t st, const int64_t* first, int keys0, bool grow) -> int {
         for (int t = 0; t < n_steps; ++t) {
             const int r = decode_body(x, st, t == 0 ? first : fb, B, kv, kv_batch, kv_max, grow ? keys0 + t : keys0,
-                                      logits, next_ids, erows, masked, tokens ? tokens + (long)t * B : nullptr);
+                                      logits, next_ids, erows, masked, tokens ? tokens + (long)t * B : nullptr,
+                                      ragged);
             if (r) return r;
         }
         return 0;
@@ -1173,7 +1258,7 @@ static int decode_step(pgmi_ctx* x, const int64_t* ids, const void* embeds, int 
         gids = x->d_ids;
     }
     if (embeds) gids = nullptr;
-    GraphKey key{B, kv, kv_batch, kv_max, logits, next_ids, gids, embeds != nullptr, masked, n_steps, tokens};
+    GraphKey key{B, kv, kv_batch, kv_max, logits, next_ids, gids, embeds != nullptr, masked, n_steps, tokens, ragged};
     GraphEntry& ge = x->graphs[key];
     if (!ge.exec) {
         if (ge.seen++ == 0) {  // first call with this key: run eagerly (sets kernel attributes)
@@ -1208,6 +1293,16 @@ int pgmi_decode_steps(pgmi_ctx* x, int64_t* ids, int B, void* kv, int kv_batch, 
     if (!ids) return fail(PGMI_E_ARG, "null argument");
     return decode_step(x, ids, nullptr, B, kv, kv_batch, kv_max, kv_len, position, logits, ids, use_graph, stream,
                        nullptr, n_steps, tokens);
+}
+
+int pgmi_decode_ragged(pgmi_ctx* x, const int64_t* ids, int B, void* kv, int kv_batch, int kv_max,
+                       const int32_t* kv_lens, const int32_t* positions, int n_steps, float* logits, int64_t* next_ids,
+                       int64_t* tokens, int use_graph, void* stream) {
+    if (!ids || !kv_lens || !positions) return fail(PGMI_E_ARG, "null argument");
+    if (n_steps > 1 && !next_ids) return fail(PGMI_E_ARG, "multi-step decode: next_ids carries the token fed back");
+    if (x && (B < 1 || B > x->c.max_batch || B > 8)) return fail(PGMI_E_ARG, "batch exceeds capacity");
+    return decode_step(x, ids, nullptr, B, kv, kv_batch, kv_max, 0, 0, logits, next_ids, use_graph, stream, nullptr,
+                       n_steps, tokens, kv_lens, positions);
 }
 
 int pgmi_decode_embeds(pgmi_ctx* x, const void* embeds, int B, void* kv, int kv_batch, int kv_max, int kv_len,

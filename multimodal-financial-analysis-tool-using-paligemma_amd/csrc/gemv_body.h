@@ -50,6 +50,8 @@ struct GemvArgs {
     const uint16_t* sinT;
     int max_pos;
     const StepState* st;
+    int st_stride;  // batch row b's record is st[b * st_stride]: 0 lock-step, 1 ragged (the RG kernels)
+    int adv_n;      // records the step's last kernel advances (LOGITS fold): 1 lock-step, nb ragged
     uint16_t* kc;
     uint16_t* vc;
     long kv_b_stride;
@@ -81,9 +83,12 @@ struct GemvArgs {
 // XREG: the activation lives in registers (lane's own K chunks), the RMSNorm is computed
 // per wave (WK == 1: every wave holds the whole row), no LDS staging / barrier; used when
 // B * K/(512*WK) chunks fit in 32 VGPRs.  Otherwise the activation is staged in LDS.
-template <int B, int KCH, int RPW, int MODE, int WK, bool XREG, int DEPTH = 1, bool EMB = false>
+// RG (GV_QKV, GV_ORES): the ragged step -- every batch row reads its own step record (RoPE row, KV-append
+// row, chunk count); the lock-step kernels (RG = false) read record 0 once and compile to what they were.
+template <int B, int KCH, int RPW, int MODE, int WK, bool XREG, int DEPTH = 1, bool EMB = false, bool RG = false>
 __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, const int nblk, uint16_t* xs) {
     static_assert(!EMB || (MODE == GV_QKV && XREG && WK == 1), "embedding fold: register-held q|k|v input only");
+    static_assert(!RG || MODE == GV_QKV || MODE == GV_ORES, "per-row step records: q|k|v and o_proj only");
     constexpr int NR = (MODE == GV_QKV || MODE == GV_GEGLU) ? 2 : 1;
     constexpr int KCW = KCH / WK;  // chunks per wave
     constexpr int NL = RPW * NR * KCW;
@@ -186,12 +191,14 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
         // a fixed order (the flash-decoding combine of k_attn_decode's partials)
         // every thread combines its own 8 outputs from the chunk records directly (stats and
         // partial rows in one round trip, no LDS staging of the weights, no barrier)
-        const int nch = (a.st->kv_len + 1 + kAttnChunk - 1) / kAttnChunk;
+        const int nch0 = (a.st->kv_len + 1 + kAttnChunk - 1) / kAttnChunk;
         constexpr int CMAX = 12;  // chunks held in registers (768 keys); longer caches take two passes
         const int nitems = a.nb * K / 8;
         for (int e8 = tid; e8 < nitems; e8 += 256) {
             const int b = e8 / (K / 8), e = (e8 % (K / 8)) * 8;
             const int h = e >> 8;
+            // ragged: row b's own chunk count (its neighbours' records past it are stale, never read)
+            const int nch = RG ? (a.st[b * a.st_stride].kv_len + 1 + kAttnChunk - 1) / kAttnChunk : nch0;
             const float* pb = a.part + (long)b * a.max_chunks * kAttnPartStride + h * 256 + (e & 255);
             const float* sp = a.part + (long)b * a.max_chunks * kAttnPartStride + 16 * 256 + h;
             float o[8];
@@ -334,7 +341,15 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
     }
 
     int kv_len = 0, pos = 0;
-    if constexpr (MODE == GV_QKV) {
+    int kv_len_r[RG ? B : 1], pos_r[RG ? B : 1];  // ragged: per batch row
+    if constexpr (MODE == GV_QKV && RG) {
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+            const StepState sb = a.st[(b < a.nb ? b : a.nb - 1) * a.st_stride];
+            kv_len_r[b] = sb.kv_len;
+            pos_r[b] = sb.position < 0 ? 0 : (sb.position > a.max_pos - 1 ? a.max_pos - 1 : sb.position);
+        }
+    } else if constexpr (MODE == GV_QKV) {
         kv_len = a.st->kv_len;
         pos = a.st->position;
         if (pos < 0) pos = 0;
@@ -363,8 +378,9 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
                 if constexpr (MODE == GV_RES || MODE == GV_ORES) {
                     pre[i][b][0] = bf2f(ldxh<false>(a.out + (long)bq * a.n_units + u));
                 } else if constexpr (MODE == GV_QKV) {
-                    pre[i][b][0] = bf2f(a.cosT[(long)pos * 128 + (u & 127)]);
-                    pre[i][b][1] = bf2f(a.sinT[(long)pos * 128 + (u & 127)]);
+                    const int pb_ = RG ? pos_r[RG ? b : 0] : pos;
+                    pre[i][b][0] = bf2f(a.cosT[(long)pb_ * 128 + (u & 127)]);
+                    pre[i][b][1] = bf2f(a.sinT[(long)pb_ * 128 + (u & 127)]);
                 }
             }
         }
@@ -452,6 +468,7 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
                 } else {  // GV_QKV
                     if (lane == 0) {
                         const int hh = u >> 7, d = u & 127;
+                        const int kvl = RG ? kv_len_r[RG ? b : 0] : kv_len;
                         const float x0 = rbf(acc[i][0][b]), x1 = rbf(acc[i][1][b]);
                         const int nh = a.I;
                         if (hh < nh + a.nkv) {
@@ -463,12 +480,12 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
                             if (hh < nh) {
                                 dst = a.out + (long)b * nh * 256 + hh * 256;
                             } else {
-                                dst = a.kc + b * a.kv_b_stride + (long)kv_len * (a.nkv * 256) + (hh - nh) * 256;
+                                dst = a.kc + b * a.kv_b_stride + (long)kvl * (a.nkv * 256) + (hh - nh) * 256;
                             }
                             stxh<false>(dst + d, o0);
                             stxh<false>(dst + d + 128, o1);
                         } else {
-                            uint16_t* dst = a.vc + b * a.kv_b_stride + (long)kv_len * (a.nkv * 256) +
+                            uint16_t* dst = a.vc + b * a.kv_b_stride + (long)kvl * (a.nkv * 256) +
                                             (hh - nh - a.nkv) * 256;
                             stxh<false>(dst + d, f2bf(x0));
                             stxh<false>(dst + d + 128, f2bf(x1));
@@ -564,6 +581,10 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
                     if (a.adv) {
                         a.adv->kv_len += 1;
                         a.adv->position += 1;
+                        for (int r = 1; r < a.adv_n; ++r) {  // the ragged step: every row's record
+                            a.adv[r].kv_len += 1;
+                            a.adv[r].position += 1;
+                        }
                     }
                 }
                 if (tid <= NSH) __hip_atomic_store(a.done + tid * STR, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -572,10 +593,10 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
     }
 }
 
-template <int B, int KCH, int RPW, int MODE, int WK, bool XREG, int DEPTH, bool EMB = false>
+template <int B, int KCH, int RPW, int MODE, int WK, bool XREG, int DEPTH, bool EMB = false, bool RG = false>
 __global__ void __launch_bounds__(256) k_gemv(GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [B][K]
-    gemv_block<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB>(a, blockIdx.x, gridDim.x, xs);
+    gemv_block<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG>(a, blockIdx.x, gridDim.x, xs);
 }
 
 }  // namespace pgmi

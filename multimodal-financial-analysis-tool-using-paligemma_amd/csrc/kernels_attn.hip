@@ -834,7 +834,11 @@ __device__ __forceinline__ void fs_vm_wait(int n) {  // s_waitcnt vmcnt(G * min(
 
 // grid (row blocks, n_kv * ns, B); key range sp = blockIdx.y % ns covers tiles [sp * tps, (sp + 1) * tps)
 // P2: scale is a power of two (Gemma: 1/16), so bf16(bf16(x) * scale) = bf16(x) * scale (one rounding)
-template <int HD, int NW, int LW, int ST, bool P2>
+// KL: ragged prefill -- batch row b attends keys [0, a.klen[b]) only.  Keys at or past the row's count are
+// neither scored (masked to -inf) nor loaded (the row index is clamped); a key range that holds none of the
+// row's keys does no tile at all and leaves (m = -1e30, l = 0, O = 0), weight exp(-1e30 - M) = 0 in the
+// combine.  KL = false: a.Lk keys for every row (the kernels as they were)
+template <int HD, int NW, int LW, int ST, bool P2, bool KL = false>
 __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int ns, int tps) {
     using I = FSInfo<HD>;
     constexpr int KS = I::KS, CT = I::CT, CH = I::CH, CR = I::CR, ROWB = I::ROWB, TILEB = I::TILEB;
@@ -846,7 +850,12 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int n
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.z, kvh = blockIdx.y / ns, sp = blockIdx.y % ns;
-    const int nt = (a.Lk + 31) / 32;
+    int Lk = a.Lk;
+    if constexpr (KL) {
+        const int kl = a.klen[b];
+        Lk = kl < 1 ? 1 : (kl < a.Lk ? kl : a.Lk);
+    }
+    const int nt = (Lk + 31) / 32;
     const int t0 = sp * tps;
     const int t1 = t0 + tps < nt ? t0 + tps : nt;
     const int ntl = t1 > t0 ? t1 - t0 : 0;
@@ -874,7 +883,7 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int n
 #pragma unroll
             for (int i = 0; i < GPW; ++i) {
                 int key = t * 32 + prow[i];
-                key = key < a.Lk ? key : a.Lk - 1;  // rows past the keys: a valid row, masked (s = -inf)
+                key = key < Lk ? key : Lk - 1;  // rows past the keys: a valid row, masked (s = -inf)
                 const uint16_t* src =
                     (pv[i] ? vbase + (long)key * a.v_row_stride : kbase + (long)key * a.k_row_stride) + pch[i] * 8;
                 __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src),
@@ -948,12 +957,12 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int n
                 const float x = rbf(ac[kt][0][j] + ac[kt][1][j]);
                 sv[kt][j] = P2 ? x * a.scale : rbf(x * a.scale);
             }
-        if (t * 32 + 32 > a.Lk) {
+        if (t * 32 + 32 > Lk) {
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (t * 32 + kt * 16 + 4 * g + j >= a.Lk) sv[kt][j] = -INFINITY;
+                    if (t * 32 + kt * 16 + 4 * g + j >= Lk) sv[kt][j] = -INFINITY;
         }
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
@@ -1108,17 +1117,17 @@ static int fs_splits(const AttnArgs& a, int HD, int QB, int want) {
     return ns < 1 ? 1 : ns;
 }
 
-template <int HD, int NW, int LW, int ST, bool P2>
+template <int HD, int NW, int LW, int ST, bool P2, bool KL = false>
 static void launch_fs_t(hipStream_t s, const AttnArgs& a, int ns, int tps, dim3 grid) {
     constexpr size_t lds = (size_t)ST * FSInfo<HD>::SLOTB;
     static_assert(lds <= 160 * 1024, "LDS");
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fs<HD, NW, LW, ST, P2>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fs<HD, NW, LW, ST, P2, KL>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = true;
     }
-    hipLaunchKernelGGL((k_attn_fs<HD, NW, LW, ST, P2>), grid, dim3(64 * (NW + LW)), lds, s, a, ns, tps);
+    hipLaunchKernelGGL((k_attn_fs<HD, NW, LW, ST, P2, KL>), grid, dim3(64 * (NW + LW)), lds, s, a, ns, tps);
 }
 
 template <int HD, int NWQ = 0>
@@ -1134,7 +1143,12 @@ static void launch_fs(hipStream_t s, const AttnArgs& a, int want_ns) {
     dim3 grid((nrows + NW * 16 - 1) / (NW * 16), a.n_kv * ns, a.B);
     int e2 = 0;
     const bool p2 = std::frexp(a.scale, &e2) == 0.5f;
-    if (p2) launch_fs_t<HD, NW, LW, ST, true>(s, a, ns, tps, grid);
+    if (a.klen) {  // ragged prefill (head dim 256, the default compute-wave count): per-row key counts
+        if constexpr (HD == 256 && NWQ == 0) {
+            if (p2) launch_fs_t<HD, NW, LW, ST, true, true>(s, a, ns, tps, grid);
+            else launch_fs_t<HD, NW, LW, ST, false, true>(s, a, ns, tps, grid);
+        }
+    } else if (p2) launch_fs_t<HD, NW, LW, ST, true>(s, a, ns, tps, grid);
     else launch_fs_t<HD, NW, LW, ST, false>(s, a, ns, tps, grid);
     if (ns > 1) {
         const long n8 = (long)a.B * a.n_kv * nrows * (HD / 8);
@@ -1186,6 +1200,10 @@ static size_t attn_full_lds(int head_dim, int Lk) {
 }
 
 void attention_prefill(hipStream_t s, int head_dim, const AttnArgs& a) {
+    if (a.klen && head_dim == 256) {  // ragged: always the one-pass key-split kernel (it honours klen)
+        launch_fs<256>(s, a, 0);
+        return;
+    }
     int v = g_attn_force;
     if (v < 0) {
         // measured on MI355X (tools/probes/attn_bench.py, round 1), us per call:
@@ -1268,15 +1286,24 @@ __global__ void __launch_bounds__(256) k_attn_decode(AttnArgs a, const StepState
     attn_decode_block(a, st, part, max_chunks, blockIdx.x, blockIdx.y, blockIdx.z, lds);
 }
 
+// the ragged step: batch row b = blockIdx.z reads its own record st[b] (a kernel of its own, so the lock-step
+// kernel above stays what it was)
+__global__ void __launch_bounds__(256) k_attn_decode_rows(AttnArgs a, const StepState* st, float* __restrict__ part,
+                                                           int max_chunks) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kAttnDecodeLds];
+    attn_decode_block(a, st + blockIdx.z, part, max_chunks, blockIdx.x, blockIdx.y, blockIdx.z, lds);
+}
+
 size_t attention_decode_part_floats(int B, int n_kv, int max_chunks) {
     return (size_t)B * n_kv * max_chunks * PSTRIDE;
 }
 
 void attention_decode(hipStream_t s, const AttnArgs& a, const StepState* st, int launch_keys, float* part,
-                      int max_chunks) {
+                      int max_chunks, int st_stride) {
     const int nch = (launch_keys + DCH - 1) / DCH;
     dim3 grid(nch < max_chunks ? nch : max_chunks, a.n_kv, a.B);
-    hipLaunchKernelGGL(k_attn_decode, grid, dim3(256), 0, s, a, st, part, max_chunks);
+    if (st_stride != 0) hipLaunchKernelGGL(k_attn_decode_rows, grid, dim3(256), 0, s, a, st, part, max_chunks);
+    else hipLaunchKernelGGL(k_attn_decode, grid, dim3(256), 0, s, a, st, part, max_chunks);
 }
 
 }  // namespace pgmi

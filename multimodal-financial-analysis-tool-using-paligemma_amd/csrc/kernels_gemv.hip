@@ -14,20 +14,20 @@ int gemv_mf_logits(hipStream_t s, const GemvArgs& a, int max_blocks);
 void gemv_mf_res(hipStream_t s, const GemvArgs& a, float* ws);
 void gemv_mf_res_norm(hipStream_t s, const GemvArgs& a, float* ws, const uint16_t* norm_w, float eps, uint16_t* hn);
 
-template <int B, int KCH, int RPW, int MODE, int WK = 1, int DEPTH = 1, bool EMB = false>
+template <int B, int KCH, int RPW, int MODE, int WK = 1, int DEPTH = 1, bool EMB = false, bool RG = false>
 static void launch_gemv(hipStream_t s, const GemvArgs& a, int max_blocks = 0) {
     constexpr bool XREG = (MODE != GV_ORES) && B * (KCH / WK) <= 8;
     size_t lds = XREG ? 0 : (size_t)B * KCH * 512 * sizeof(uint16_t);
     static size_t attr = 0;  // largest dynamic LDS size granted so far
     if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = lds;
     }
     constexpr int per_block = (4 / WK) * RPW;
     int blocks = (a.n_units + per_block - 1) / per_block;
     if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
-    hipLaunchKernelGGL((k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB>), dim3(blocks), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG>), dim3(blocks), dim3(256), lds, s, a);
 }
 
 // K = 2048 (hidden); nh q heads, nkv kv heads of 256
@@ -36,14 +36,17 @@ bool gemv_qkv_folds_embed(int B) { return B <= 2 && B < gemv_mf_min_batch(); }
 void gemv_qkv(hipStream_t s, int B, int nh, int nkv, const uint16_t* h, const uint16_t* norm_w, float eps,
               const uint16_t* Wqkv, const uint16_t* cosT, const uint16_t* sinT, int max_pos, const StepState* st,
               uint16_t* q_out, uint16_t* kc, uint16_t* vc, long kv_b_stride, float* ws, const EmbedFold* emb,
-              const uint16_t* Wf) {
+              const uint16_t* Wf, int st_stride) {
     GemvArgs a{};
     a.x = h; a.norm_w = norm_w; a.eps = eps; a.W = Wqkv; a.n_units = (nh + 2 * nkv) * 128; a.K = 2048; a.nb = B;
     a.I = nh; a.out = q_out; a.cosT = cosT; a.sinT = sinT; a.max_pos = max_pos; a.st = st; a.kc = kc; a.vc = vc;
-    a.kv_b_stride = kv_b_stride; a.nkv = nkv;
+    a.kv_b_stride = kv_b_stride; a.nkv = nkv; a.st_stride = st_stride;
+    // per-row step records (st_stride != 0): the RG kernels; one row reads record 0 either way
+    const bool rg = st_stride != 0 && B > 1;
     if (emb) {  // layer 0: the token's embedding row is the input (and is written to h)
         a.ids = emb->ids; a.E = emb->E; a.normalizer = emb->normalizer; a.pad_id = emb->pad_id; a.emb_out = emb->h_out;
         if (B <= 1) launch_gemv<1, 4, 1, GV_QKV, 1, 1, true>(s, a);
+        else if (rg) launch_gemv<2, 4, 1, GV_QKV, 1, 1, true, true>(s, a);
         else launch_gemv<2, 4, 1, GV_QKV, 1, 1, true>(s, a);
         return;
     }
@@ -54,6 +57,7 @@ void gemv_qkv(hipStream_t s, int B, int nh, int nkv, const uint16_t* h, const ui
         return;
     }
     if (B <= 1) L_(1, 4, 1, GV_QKV);
+    else if (rg) launch_gemv<2, 4, 1, GV_QKV, 1, 1, false, true>(s, a);
     else L_(2, 4, 1, GV_QKV);  // B >= 3 runs on MFMA (above)
 }
 
@@ -99,10 +103,12 @@ void gemv_res_norm(hipStream_t s, int B, int K, const uint16_t* x, const uint16_
 }
 
 void gemv_o_attn(hipStream_t s, int B, int G, const float* part, int max_chunks, const StepState* st,
-                 const uint16_t* Wo, int N, uint16_t* h_inout, uint16_t* o_out, float* ssq, const uint16_t* Wf) {
+                 const uint16_t* Wo, int N, uint16_t* h_inout, uint16_t* o_out, float* ssq, const uint16_t* Wf,
+                 int st_stride) {
     GemvArgs a{};
     a.x = nullptr; a.norm_w = nullptr; a.W = Wo; a.n_units = N; a.K = G * 256; a.nb = B; a.out = h_inout;
     a.part = part; a.max_chunks = max_chunks; a.G = G; a.st = st; a.o_out = o_out;
+    a.st_stride = st_stride;
     if (B >= gemv_mf_min_batch() && o_out) {
         a.ssq = ssq;
         a.Wf = N % 16 == 0 ? Wf : nullptr;
@@ -112,6 +118,7 @@ void gemv_o_attn(hipStream_t s, int B, int G, const float* part, int max_chunks,
     // grid capped so each workgroup's combine prologue is amortised over 8 output rows (256 / 128 / 64
     // measured in round 4: 952 / 928-939 / 894-899 tok/s, profiles/r04_b1_probes_ab.txt)
     if (B <= 1) launch_gemv<1, 4, 2, GV_ORES>(s, a, 256);
+    else if (B <= 2 && st_stride != 0) launch_gemv<2, 4, 2, GV_ORES, 1, 1, false, true>(s, a, 256);
     else if (B <= 2) launch_gemv<2, 4, 2, GV_ORES>(s, a, 256);
     else if (B <= 4) launch_gemv<4, 4, 1, GV_ORES>(s, a, 256);
     else launch_gemv<8, 4, 1, GV_ORES>(s, a, 256);
@@ -138,7 +145,7 @@ bool gemv_logits_folds(int B) { return B < gemv_mf_min_batch(); }
 
 bool gemv_logits(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w, float eps, const uint16_t* E,
                  int V, float* logits, float* pmax, int* pidx, int* nparts, unsigned* done, int64_t* next,
-                 StepState* adv, int64_t* hist) {
+                 StepState* adv, int64_t* hist, int adv_n) {
     GemvArgs a{};
     a.x = h; a.norm_w = norm_w; a.eps = eps; a.W = E; a.n_units = V; a.K = 2048; a.nb = B; a.logits = logits;
     a.pmax = pmax; a.pidx = pidx;
@@ -153,6 +160,7 @@ bool gemv_logits(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w
         a.done = done;
         a.next = next;
         a.adv = adv;
+        a.adv_n = adv_n;
         a.hist = hist;
     }
 #define LG_(b_, rpw)                                                    \

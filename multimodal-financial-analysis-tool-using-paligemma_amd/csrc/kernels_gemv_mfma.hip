@@ -139,8 +139,11 @@ void mf_swizzle(hipStream_t s, const uint16_t* W, int rows, int K, uint16_t* out
 #ifndef PGMI_MF_NT
 #define PGMI_MF_NT 2
 #endif
-template <int MODE, int NR, int KW, int WK, int PF = 1, bool NS = false, bool SW = false>
+// RG (GV_QKV): the ragged step -- batch row b takes its RoPE row and KV-append row from its own step record
+// st[b * st_stride]; RG = false reads record 0 once for every row (the lock-step kernels, unchanged)
+template <int MODE, int NR, int KW, int WK, int PF = 1, bool NS = false, bool SW = false, bool RG = false>
 __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restrict__ ws) {
+    static_assert(!RG || MODE == GV_QKV, "per-row step records: q|k|v only");
     constexpr int NKB = KW / 128;          // 128-wide k blocks per wave
     constexpr bool STAGE = (MODE != GV_RES) && !NS;
     // (the fragment-major image, SW: every load reads whole lines once -- non-temporal)
@@ -291,7 +294,7 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
     // RoPE operands of this workgroup's first group, fetched with the weight stream (the epilogue
     // would otherwise pay their round trip after the reduction)
     float cs0 = 0.f, sn0 = 0.f;
-    if constexpr (MODE == GV_QKV) {
+    if constexpr (MODE == GV_QKV && !RG) {
         int p0 = a.st->position;
         p0 = p0 < 0 ? 0 : (p0 > a.max_pos - 1 ? a.max_pos - 1 : p0);
         const int d0 = (grp & 15) * 8 + (n & 7);
@@ -335,7 +338,16 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
     }
 
     int kv_len = 0, pos = 0;
-    if constexpr (MODE == GV_QKV) {
+    int kv_len_r[RG ? 4 : 1], pos_r[RG ? 4 : 1];  // ragged: this lane's four batch rows b = 4g + r
+    if constexpr (MODE == GV_QKV && RG) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int b = 4 * g + r;
+            const StepState sb = a.st[(b < a.nb ? b : a.nb - 1) * a.st_stride];
+            kv_len_r[r] = sb.kv_len;
+            pos_r[r] = sb.position < 0 ? 0 : (sb.position > a.max_pos - 1 ? a.max_pos - 1 : sb.position);
+        }
+    } else if constexpr (MODE == GV_QKV) {
         kv_len = a.st->kv_len;
         pos = a.st->position;
         if (pos < 0) pos = 0;
@@ -394,15 +406,22 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
                 const int b = 4 * g + r;
                 if (b >= a.nb) break;
                 const float x0 = rbf(hi ? part[r] : acc[0][r]), x1 = rbf(hi ? acc[0][r] : part[r]);
+                const int kvl = RG ? kv_len_r[RG ? r : 0] : kv_len;
                 if (hh < nh + a.nkv) {
-                    const float c = cur == grp0 ? cs0 : bf2f(a.cosT[(long)pos * 128 + d]);
-                    const float sn = cur == grp0 ? sn0 : bf2f(a.sinT[(long)pos * 128 + d]);
+                    float c, sn;
+                    if constexpr (RG) {
+                        c = bf2f(a.cosT[(long)pos_r[RG ? r : 0] * 128 + d]);
+                        sn = bf2f(a.sinT[(long)pos_r[RG ? r : 0] * 128 + d]);
+                    } else {
+                        c = cur == grp0 ? cs0 : bf2f(a.cosT[(long)pos * 128 + d]);
+                        sn = cur == grp0 ? sn0 : bf2f(a.sinT[(long)pos * 128 + d]);
+                    }
                     const uint16_t o = hi ? f2bf(rbf(x1 * c) + rbf(x0 * sn)) : f2bf(rbf(x0 * c) + rbf(-x1 * sn));
                     uint16_t* dst = hh < nh ? a.out + (long)b * nh * 256 + hh * 256
-                                            : a.kc + b * a.kv_b_stride + (long)kv_len * (a.nkv * 256) + (hh - nh) * 256;
+                                            : a.kc + b * a.kv_b_stride + (long)kvl * (a.nkv * 256) + (hh - nh) * 256;
                     dst[d + hi * 128] = o;
                 } else {
-                    uint16_t* dst = a.vc + b * a.kv_b_stride + (long)kv_len * (a.nkv * 256) + (hh - nh - a.nkv) * 256;
+                    uint16_t* dst = a.vc + b * a.kv_b_stride + (long)kvl * (a.nkv * 256) + (hh - nh - a.nkv) * 256;
                     dst[d + hi * 128] = f2bf(hi ? x1 : x0);
                 }
             }
@@ -664,11 +683,15 @@ __global__ void __launch_bounds__(256, 1) k_gemv_ml(GemvArgs a, float* __restric
 // As that prologue: up to CMAX chunk records are loaded unconditionally up front (chunk index
 // clamped, records past nch ignored), so the combine costs one memory round trip instead of one
 // per chunk; 64-thread workgroups spread the 2,048 threads of B = 8 over 32 CUs.
+// RG: the ragged step -- row b's own chunk count from its record st[b * st_stride] (an instance of its own: the
+// lock-step instance reads the shared record with one scalar load, as it did)
+template <bool RG>
 __global__ void __launch_bounds__(64) k_attn_combine(GemvArgs a, uint16_t* __restrict__ o, int K) {
     const int e8 = blockIdx.x * 64 + threadIdx.x;
     if (e8 >= a.nb * K / 8) return;
-    const int nch = (a.st->kv_len + 1 + kAttnChunk - 1) / kAttnChunk;
+    const int nch0 = (a.st->kv_len + 1 + kAttnChunk - 1) / kAttnChunk;
     const int b = e8 / (K / 8), e = (e8 % (K / 8)) * 8;
+    const int nch = RG ? (a.st[b * a.st_stride].kv_len + 1 + kAttnChunk - 1) / kAttnChunk : nch0;
     const int h = e >> 8;
     const float* pb = a.part + (long)b * a.max_chunks * kAttnPartStride + h * 256 + (e & 255);
     const float* sp = a.part + (long)b * a.max_chunks * kAttnPartStride + 16 * 256 + h;
@@ -827,16 +850,16 @@ void rows_norm(hipStream_t s, const uint16_t* x, const uint16_t* w, float eps, i
 // smallest lock-step batch whose decode projections run on MFMA (B <= 2: the v_dot2 GEMVs of gemv_body.h)
 int gemv_mf_min_batch() { return 3; }
 
-template <int MODE, int NR, int KW, int WK, int PF = 1, bool NS = false, bool SW = false>
+template <int MODE, int NR, int KW, int WK, int PF = 1, bool NS = false, bool SW = false, bool RG = false>
 static void launch_mf(hipStream_t s, const GemvArgs& a, int blocks, int KS, float* ws) {
     const size_t lds = (MODE == GV_RES || NS) ? 0 : (size_t)a.nb * (a.K + 8) * sizeof(uint16_t);
     static size_t attr = 0;
     if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = lds;
     }
-    hipLaunchKernelGGL((k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW>), dim3(blocks, KS), dim3(64 * WK), lds, s, a, ws);
+    hipLaunchKernelGGL((k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG>), dim3(blocks, KS), dim3(64 * WK), lds, s, a, ws);
 }
 
 static int groups_of(int units) { return (units + 15) / 16; }
@@ -866,6 +889,17 @@ static int ms_blocks(int units, int cap) {
 void gemv_mf_qkv(hipStream_t s, const GemvArgs& a, float* /*ws*/) {
     GemvArgs r = a;
     r.n_units = 2 * a.n_units;
+    if (a.st_stride != 0) {  // the ragged step: per-row RoPE / KV-append rows (RG kernels)
+        if (a.Wf) {
+            r.W = a.Wf;
+            if (a.norm_w) launch_mf<GV_QKV, 1, 256, 8, 1, false, true, true>(s, r, groups_of(r.n_units), 1, nullptr);
+            else launch_mf<GV_QKV, 1, 256, 8, 1, true, true, true>(s, r, groups_of(r.n_units), 1, nullptr);
+            return;
+        }
+        if (a.norm_w) launch_mf<GV_QKV, 1, 256, 8, 1, false, false, true>(s, r, groups_of(r.n_units), 1, nullptr);
+        else launch_mf<GV_QKV, 1, 256, 8, 1, true, false, true>(s, r, groups_of(r.n_units), 1, nullptr);
+        return;
+    }
     if (a.Wf) {  // the fragment-major weight image in the GEMV's row order (the decode step passes it)
         r.W = a.Wf;
         if (a.norm_w) launch_mf<GV_QKV, 1, 256, 8, 1, false, true>(s, r, groups_of(r.n_units), 1, nullptr);
@@ -905,7 +939,9 @@ void gemv_mf_geglu(hipStream_t s, const GemvArgs& a) {  // K = 2048, gate|up row
 // o_proj: combine the attention partials once (-> o, bf16 [nb][K]), then the residual GEMV
 void gemv_mf_ores(hipStream_t s, const GemvArgs& a, uint16_t* o) {
     const int K = a.K;
-    hipLaunchKernelGGL(k_attn_combine, dim3((a.nb * K / 8 + 63) / 64), dim3(64), 0, s, a, o, K);
+    if (a.st_stride != 0)
+        hipLaunchKernelGGL(k_attn_combine<true>, dim3((a.nb * K / 8 + 63) / 64), dim3(64), 0, s, a, o, K);
+    else hipLaunchKernelGGL(k_attn_combine<false>, dim3((a.nb * K / 8 + 63) / 64), dim3(64), 0, s, a, o, K);
     GemvArgs r = a;
     r.x = o;
     r.norm_w = nullptr;

@@ -139,15 +139,16 @@ void embed_rows(hipStream_t s, const int64_t* ids, int rows, const uint16_t* E, 
 
 // ---------------------------------------------------------------- merge (prefill)
 // masked_scatter order: the k-th <image> token (row-major over B x L) takes image row k.
+// lens (may be null; rows of L slots): slots at or past a row's length are padding, never <image> tokens
 __global__ void __launch_bounds__(1024) k_image_scan(const int64_t* __restrict__ ids, int n, int64_t image_token,
-                                                     int* __restrict__ idx) {
+                                                     int* __restrict__ idx, const int* __restrict__ lens, int L) {
     __shared__ int warp_tot[16];
     __shared__ int carry;
     if (threadIdx.x == 0) carry = 0;
     __syncthreads();
     for (int base = 0; base < n; base += 1024) {
         const int i = base + threadIdx.x;
-        const int f = (i < n && ids[i] == image_token) ? 1 : 0;
+        const int f = (i < n && ids[i] == image_token && (!lens || i % L < lens[i / L])) ? 1 : 0;
         // inclusive scan within the wave
         int v = f;
         const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -170,9 +171,12 @@ __global__ void __launch_bounds__(1024) k_image_scan(const int64_t* __restrict__
 __global__ void k_merge(const int64_t* __restrict__ ids, const int* __restrict__ img_idx,
                         const uint16_t* __restrict__ E, int D, const uint16_t* __restrict__ img, int n_img_rows,
                         int64_t pad_id, float sqrt_h, float normalizer,
-                        const uint16_t* __restrict__ embeds_in, uint16_t* __restrict__ out) {
+                        const uint16_t* __restrict__ embeds_in, uint16_t* __restrict__ out,
+                        const int* __restrict__ lens, int L) {
     const long r = blockIdx.x;
-    const int64_t id = ids[r];
+    // a ragged batch's pad slot: a zero row, its id never looked up
+    const bool padslot = lens && (int)(r % L) >= lens[r / L];
+    const int64_t id = padslot ? pad_id : ids[r];
     const int k = img_idx[r];
     for (int c = threadIdx.x * 8; c < D; c += blockDim.x * 8) {
         u16x8 o;
@@ -187,7 +191,7 @@ __global__ void k_merge(const int64_t* __restrict__ ids, const int* __restrict__
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o.v[j] = 0;
             }
-        } else if (id == pad_id) {
+        } else if (id == pad_id || padslot) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) o.v[j] = 0;
         } else {
@@ -202,11 +206,26 @@ __global__ void k_merge(const int64_t* __restrict__ ids, const int* __restrict__
 
 void merge_embed(hipStream_t s, const int64_t* ids, int B, int L, const uint16_t* E, int D, const uint16_t* img,
                  int n_img_rows, int64_t image_token, int64_t pad_id, float sqrt_h, float normalizer,
-                 const uint16_t* embeds_in, int* scan_buf, uint16_t* out) {
+                 const uint16_t* embeds_in, int* scan_buf, uint16_t* out, const int* lens) {
     const int n = B * L;
-    hipLaunchKernelGGL(k_image_scan, dim3(1), dim3(1024), 0, s, ids, n, image_token, scan_buf);
+    hipLaunchKernelGGL(k_image_scan, dim3(1), dim3(1024), 0, s, ids, n, image_token, scan_buf, lens, L);
     hipLaunchKernelGGL(k_merge, dim3(n), dim3(256), 0, s, ids, scan_buf, E, D, img, n_img_rows, pad_id, sqrt_h,
-                       normalizer, embeds_in, out);
+                       normalizer, embeds_in, out, lens, L);
+}
+
+// out[b] = x[b][lens[b] - 1]: the last real token's row of each sequence of a ragged batch
+__global__ void k_gather_last_rows(const uint16_t* __restrict__ x, int L, int D, const int* __restrict__ lens,
+                                   uint16_t* __restrict__ out) {
+    const int b = blockIdx.x;
+    int l = lens[b];
+    l = l < 1 ? 1 : (l > L ? L : l);
+    const uint16_t* src = x + ((long)b * L + (l - 1)) * D;
+    for (int c = threadIdx.x * 8; c < D; c += blockDim.x * 8)
+        *reinterpret_cast<uint4*>(out + (long)b * D + c) = ldg16(src + c);
+}
+
+void gather_last_rows(hipStream_t s, const uint16_t* x, int B, int L, int D, const int* lens, uint16_t* out) {
+    hipLaunchKernelGGL(k_gather_last_rows, dim3(B), dim3(256), 0, s, x, L, D, lens, out);
 }
 
 __global__ void k_scale(const uint16_t* __restrict__ x, long n, float a, uint16_t* __restrict__ out) {
@@ -498,13 +517,15 @@ void pad_rows(hipStream_t s, const uint16_t* src, int rows, int K, int Kpad, uin
 
 // ---------------------------------------------------------------- argmax (first max, torch semantics)
 __global__ void k_argmax_finish(const float* __restrict__ pmax, const int* __restrict__ pidx, int nparts,
-                                int64_t* __restrict__ out, StepState* adv, int64_t* __restrict__ hist) {
+                                int64_t* __restrict__ out, StepState* adv, int adv_n,
+                                int64_t* __restrict__ hist) {
     const int b = blockIdx.x;
     // the decode step's last kernel: every reader of the step state is done, so advance it to
     // the next step's (kv_len + 1, position + 1); pgmi_decode then skips its host-side set
-    if (adv && b == 0 && threadIdx.x == 0) {
-        adv->kv_len += 1;
-        adv->position += 1;
+    // (adv_n records: the shared one on the lock-step path, row b's own on the ragged one)
+    if (adv && b < adv_n && threadIdx.x == 0) {
+        adv[b].kv_len += 1;
+        adv[b].position += 1;
     }
     float best = -INFINITY;
     int bi = 0x7fffffff;
@@ -536,8 +557,8 @@ __global__ void k_argmax_finish(const float* __restrict__ pmax, const int* __res
 }
 
 void argmax_finish(hipStream_t s, int B, const float* pmax, const int* pidx, int nparts, int64_t* out,
-                   StepState* adv, int64_t* hist) {
-    hipLaunchKernelGGL(k_argmax_finish, dim3(B), dim3(256), 0, s, pmax, pidx, nparts, out, adv, hist);
+                   StepState* adv, int64_t* hist, int adv_n) {
+    hipLaunchKernelGGL(k_argmax_finish, dim3(B), dim3(256), 0, s, pmax, pidx, nparts, out, adv, adv_n, hist);
 }
 
 // ---------------------------------------------------------------- stop tokens of the batched loop
@@ -625,7 +646,7 @@ void argmax_rows(hipStream_t s, const float* x, int rows, int V, float* pmax, in
     const int slice = ((V + nb - 1) / nb + 3) & ~3;
     nb = (V + slice - 1) / slice;
     hipLaunchKernelGGL(k_argmax_part, dim3(nb, rows), dim3(256), 0, s, x, V, slice, pmax, pidx, out);
-    if (nb > 1) hipLaunchKernelGGL(k_argmax_finish, dim3(rows), dim3(256), 0, s, pmax, pidx, nb, out, nullptr, nullptr);
+    if (nb > 1) hipLaunchKernelGGL(k_argmax_finish, dim3(rows), dim3(256), 0, s, pmax, pidx, nb, out, nullptr, 0, nullptr);
 }
 
 // ---------------------------------------------------------------- synthetic weights (bench / tests)
@@ -656,6 +677,31 @@ void fill_synthetic(hipStream_t s, uint16_t* dst, long n, uint64_t key, float sc
 __global__ void k_set_step(StepState* st, int kv_len, int position) {
     st->kv_len = kv_len;
     st->position = position;
+}
+
+// the ragged step's records, one per batch row, from the caller's host arrays (passed by value)
+__global__ void k_set_step_rows(StepState* st, RowInts kv_lens, RowInts positions, int B) {
+    const int b = threadIdx.x;
+    if (b < B && b < 8) {
+        st[b].kv_len = kv_lens.v[b];
+        st[b].position = positions.v[b];
+    }
+}
+
+void set_step_rows(hipStream_t s, StepState* st, const RowInts& kv_lens, const RowInts& positions, int B) {
+    hipLaunchKernelGGL(k_set_step_rows, dim3(1), dim3(64), 0, s, st, kv_lens, positions, B);
+}
+
+__global__ void k_set_row_ints(int* dst, RowInts a, RowInts b2, int B) {
+    const int b = threadIdx.x;
+    if (b < B && b < 8) {
+        dst[b] = a.v[b];
+        dst[8 + b] = b2.v[b];
+    }
+}
+
+void set_row_ints(hipStream_t s, int* dst, const RowInts& a, const RowInts& b2, int B) {
+    hipLaunchKernelGGL(k_set_row_ints, dim3(1), dim3(64), 0, s, dst, a, b2, B);
 }
 
 void set_step(hipStream_t s, StepState* st, int kv_len, int position) {

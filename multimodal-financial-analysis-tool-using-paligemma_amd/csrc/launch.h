@@ -70,6 +70,10 @@ struct StepState {  // device-resident decode step (read by kernels -> graph-rep
     int kv_len;     // index the new token's K/V is written at (= KVCache.num_items())
     int position;   // rotary position (= attention_mask.cumsum(-1)[:, -1], modeling_gemma.py:526)
 };
+// The record is an array: batch row b reads st[b * st_stride].  st_stride = 0 is the lock-step step (one
+// record shared by every row), st_stride = 1 the ragged step (pgmi_decode_ragged: a record per row, each
+// row with its own KV write row, attended key count and rotary position).  The step's last kernel
+// advances records [0, adv_n): 1 on the lock-step path, B on the ragged one.
 
 // decode layer 0: the embedding lookup folded into the q|k|v GEMV (h_out receives the scaled row)
 struct EmbedFold {
@@ -84,7 +88,8 @@ bool gemv_qkv_folds_embed(int B);  // batches the fold covers (the register-inpu
 void gemv_qkv(hipStream_t s, int B, int nh, int nkv, const uint16_t* h, const uint16_t* norm_w, float eps,
               const uint16_t* Wqkv, const uint16_t* cosT, const uint16_t* sinT, int max_pos, const StepState* st,
               uint16_t* q_out, uint16_t* kc, uint16_t* vc, long kv_b_stride, float* ws = nullptr,
-              const EmbedFold* emb = nullptr, const uint16_t* Wf = nullptr);  // Wf: as gemv_geglu's
+              const EmbedFold* emb = nullptr, const uint16_t* Wf = nullptr,  // Wf: as gemv_geglu's
+              int st_stride = 0);
 // ws: fp32 scratch (>= 4 x B x N floats) for the MFMA path's K split of K = 16384 (B >= 3)
 void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W, int N, uint16_t* h_inout,
               float* ws);
@@ -103,7 +108,7 @@ void rows_norm(hipStream_t s, const uint16_t* x, const uint16_t* w, float eps, i
 // new h, [B][N / 16] -- the next RMSNorm's, read by gemv_geglu
 void gemv_o_attn(hipStream_t s, int B, int G, const float* part, int max_chunks, const StepState* st,
                  const uint16_t* Wo, int N, uint16_t* h_inout, uint16_t* o_out, float* ssq = nullptr,
-                 const uint16_t* Wf = nullptr);
+                 const uint16_t* Wf = nullptr, int st_stride = 0);
 // fused RMSNorm + gate|up + GeGLU; ssq (B >= gemv_mf_min_batch() only): h's RMSNorm from the
 // partials gemv_o_attn wrote instead of the row pass; Wf (idem): the gate|up weights' fragment-major
 // image (mf_swizzle: the gate rows', then the up rows'), read instead of Wgu
@@ -116,11 +121,11 @@ int gemv_mf_min_batch();  // smallest batch on the MFMA decode projections
 bool gemv_logits(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w, float eps,
                  const uint16_t* E, int V, float* logits, float* pmax, int* pidx, int* nparts,
                  unsigned* done = nullptr, int64_t* next = nullptr, StepState* adv = nullptr,
-                 int64_t* hist = nullptr);
+                 int64_t* hist = nullptr, int adv_n = 1);
 // adv (may be null): the decode step state, advanced by one step (the step's last kernel); hist (may be
 // null): a second destination of the argmax (a multi-step graph's per-step token record)
 void argmax_finish(hipStream_t s, int B, const float* pmax, const int* pidx, int nparts, int64_t* out,
-                   StepState* adv = nullptr, int64_t* hist = nullptr);
+                   StepState* adv = nullptr, int64_t* hist = nullptr, int adv_n = 1);
 int argmax_scratch_parts();
 void argmax_rows(hipStream_t s, const float* x, int rows, int V, float* pmax, int* pidx, int64_t* out);
 void eos_update(hipStream_t s, int64_t* next, int* finished, int B, int64_t eos, int64_t pad, int* n_alive);
@@ -146,13 +151,16 @@ struct AttnArgs {
     long mask_b_stride;
     int mask_k_stride;
     int mask_round;
+    // ragged prefill: batch row b attends keys [0, klen[b]) (a device array, klen[b] <= Lk); nullptr: Lk
+    // keys for every row.  Honoured by the one-pass key-split kernel, which ragged prefills always take
+    const int* klen;
 };
 void attention_prefill(hipStream_t s, int head_dim, const AttnArgs& a);
 // decode: Lq == 1, rows = the G heads; keys split over chunks; kv length from StepState (+1)
 // flash-decoding over 64-key chunks (partials only; the combine is gemv_o_attn's prologue);
 // launch_keys = upper bound on kv_len+1 this call
 void attention_decode(hipStream_t s, const AttnArgs& a, const StepState* st, int launch_keys, float* part,
-                      int max_chunks);
+                      int max_chunks, int st_stride = 0);
 constexpr int kAttnChunk = 64;
 constexpr int kAttnPartStride = 16 * 256 + 32;  // floats per (b, kv head, chunk) record
 size_t attention_decode_part_floats(int B, int n_kv, int max_chunks);
@@ -193,9 +201,21 @@ void layernorm(hipStream_t s, const uint16_t* x, const uint16_t* w, const uint16
 void embed_rows(hipStream_t s, const int64_t* ids, int rows, const uint16_t* E, int D, float normalizer,
                 int64_t pad_id, uint16_t* out);
 // merge (modeling_gemma.py:468-537) + GemmaModel normalizer (:367-368)
+// lens (may be null): row b's tokens are ids[b][0 .. lens[b]); the slots past them are padding -- zero rows,
+// their ids never looked up (nor counted as <image> tokens)
 void merge_embed(hipStream_t s, const int64_t* ids, int B, int L, const uint16_t* E, int D,
                  const uint16_t* img, int n_img_rows, int64_t image_token, int64_t pad_id, float sqrt_h,
-                 float normalizer, const uint16_t* embeds_in, int* scan_buf, uint16_t* out);
+                 float normalizer, const uint16_t* embeds_in, int* scan_buf, uint16_t* out,
+                 const int* lens = nullptr);
+// out[b] = x[b][lens[b] - 1] (rows of D bf16, D % 8 == 0): each sequence's last real token of a ragged batch
+void gather_last_rows(hipStream_t s, const uint16_t* x, int B, int L, int D, const int* lens, uint16_t* out);
+// per-row host values handed to a setter kernel by value (B <= 8 rows, pgmi_create's max_batch bound): no
+// staging copy, and nothing of the host arrays is read after the launch call returns
+struct RowInts { int v[8]; };
+// the ragged step's per-row records: st[b] = {kv_lens.v[b], positions.v[b]}
+void set_step_rows(hipStream_t s, StepState* st, const RowInts& kv_lens, const RowInts& positions, int B);
+// dst[b] = a.v[b], dst[8 + b] = b2.v[b] (a ragged prefill's token counts and attended key counts)
+void set_row_ints(hipStream_t s, int* dst, const RowInts& a, const RowInts& b2, int B);
 void scale_rows(hipStream_t s, const uint16_t* x, long n, float normalizer, uint16_t* out);
 void add_rows(hipStream_t s, const uint16_t* x, const uint16_t* y, long n, uint16_t* out);  // bf16(x + y), n % 8 == 0
 // qkv: bf16 [B*L][(nh+2nkv)*256], or (split > 1) the fp32 partial slabs ws[split][B*L][...]

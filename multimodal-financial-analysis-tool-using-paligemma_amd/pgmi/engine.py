@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from . import _native as N
+from . import ragged as R
 
 
 def config_dict(cfg) -> dict:
@@ -79,6 +80,7 @@ class Engine:
             self.views[name.value.decode()] = self.slab[off.value: off.value + 2 * numel].view(torch.bfloat16).view(shp)
         self.prepared = False
         self._logits_buf = {}
+        self._ragged_buf = {}
 
     def __del__(self):
         try:
@@ -249,12 +251,18 @@ class Engine:
         return out
 
     def lm_forward(self, kv: torch.Tensor, kv_start: int, positions, ids=None, image_feats=None, embeds=None,
-                   logits_rows: int = 0) -> torch.Tensor:
+                   logits_rows: int = 0, lens=None) -> torch.Tensor:
         """GemmaForCausalLM.forward over merged embeddings (see pgmi.h).  Returns fp32 logits
         (B, L, V) (logits_rows 0) or (B, 1, V): logits_rows 1 keeps every row's final hidden state
         for final_hidden / lazy all-row logits; 2 needs only the last row's, so the last layer's
-        post-attention work runs for the last row alone (the KV cache is written for every row)."""
+        post-attention work runs for the last row alone (the KV cache is written for every row).
+
+        lens (B ints, optional): a ragged batch -- row b's tokens are ids[b, :lens[b]], the rest of the
+        row is right padding (pgmi_lm_forward_ragged): each row attends its own real tokens only, pad
+        ids are never looked up, and logits_rows 1 / 2 return each row's logits at token lens[b] - 1."""
         self._ready()
+        if lens is not None and embeds is not None:
+            raise ValueError("lm_forward: a ragged batch (lens) takes token ids, not embeds")
         if embeds is not None:
             e = embeds.to(self.device, torch.bfloat16).contiguous()
             B, L = e.shape[0], e.shape[1]
@@ -273,6 +281,15 @@ class Engine:
         pos = torch.broadcast_to(pos.reshape(pos.shape[0] if pos.dim() > 1 else 1, -1), (B, L)).contiguous()
         V = self.cfgd["t_vocab"]
         out = torch.empty((B, L if logits_rows == 0 else 1, V), dtype=torch.float32, device=self.device)
+        if lens is not None:
+            ln = torch.as_tensor(lens).detach().to("cpu", torch.int32).reshape(-1).contiguous()
+            if ln.numel() != B:
+                raise ValueError(f"lens has {ln.numel()} entries for a batch of {B}")
+            N.check(self.lib.pgmi_lm_forward_ragged(self.ctx, idp, imgp, nimg, None, B, L, pos.data_ptr(),
+                                                    ln.data_ptr(), kv.data_ptr(), kv.shape[2], kv.shape[3], kv_start,
+                                                    out.data_ptr(), logits_rows, self._s()),
+                    "pgmi_lm_forward_ragged")
+            return out
         N.check(self.lib.pgmi_lm_forward(self.ctx, idp, imgp, nimg, N.ptr(e), B, L, pos.data_ptr(), kv.data_ptr(),
                                          kv.shape[2], kv.shape[3], kv_start, out.data_ptr(), logits_rows, self._s()),
                 "pgmi_lm_forward")
@@ -324,6 +341,39 @@ class Engine:
         N.check(self.lib.pgmi_decode_steps(self.ctx, ids.data_ptr(), B, kv.data_ptr(), kv.shape[2], kv.shape[3], kv_len,
                                            position, int(n_steps), logits.data_ptr(), N.ptr(tokens), int(graph),
                                            self._s()), "pgmi_decode_steps")
+        return logits
+
+    def decode_ragged(self, ids: torch.Tensor, kv: torch.Tensor, kv_lens, positions, n_steps: int = 1,
+                      logits: torch.Tensor = None, tokens: torch.Tensor = None, next_ids: torch.Tensor = None,
+                      graph: bool = False) -> torch.Tensor:
+        """n_steps decode steps for B rows of different lengths (pgmi_decode_ragged): at step t row b writes
+        its K/V at row kv_lens[b] + t, attends keys [0, kv_lens[b] + t] and uses rotary position
+        positions[b] + t.  kv_lens / positions: B host ints each.  n_steps > 1 feeds each step's argmax back
+        through next_ids (default: ids, in place, which must then be a contiguous int64 device tensor);
+        tokens (int64 (n_steps, B), optional) records them.  Returns the last step's logits (B, V) fp32."""
+        self._ready()
+        if ids.dtype is not torch.int64 or ids.device != self.device or not ids.is_contiguous():
+            if n_steps > 1 and next_ids is None:
+                raise ValueError("decode_ragged: ids must be a contiguous int64 tensor on the engine's device "
+                                 "(updated in place when n_steps > 1)")
+            ids = ids.to(self.device, torch.int64).contiguous()
+        ids = ids.view(-1)
+        B = ids.numel()
+        kl = torch.as_tensor(kv_lens).detach().to("cpu", torch.int32).reshape(-1).contiguous()
+        ps = torch.as_tensor(positions).detach().to("cpu", torch.int32).reshape(-1).contiguous()
+        if kl.numel() != B or ps.numel() != B:
+            raise ValueError(f"decode_ragged: kv_lens / positions need {B} entries each")
+        if n_steps > 1 and next_ids is None:
+            next_ids = ids
+        if logits is None:
+            logits = torch.empty((B, self.cfgd["t_vocab"]), dtype=torch.float32, device=self.device)
+        if tokens is not None and (tokens.dtype is not torch.int64 or tokens.device != self.device
+                                   or not tokens.is_contiguous() or tokens.numel() < n_steps * B):
+            raise ValueError("decode_ragged: tokens must be a contiguous int64 (n_steps, B) tensor on the device")
+        N.check(self.lib.pgmi_decode_ragged(self.ctx, ids.data_ptr(), B, kv.data_ptr(), kv.shape[2], kv.shape[3],
+                                            kl.data_ptr(), ps.data_ptr(), int(n_steps), logits.data_ptr(),
+                                            N.ptr(next_ids), N.ptr(tokens), int(graph), self._s()),
+                "pgmi_decode_ragged")
         return logits
 
     def decode_embeds(self, embeds: torch.Tensor, kv: torch.Tensor, kv_len: int, position: int,
@@ -414,7 +464,8 @@ class Engine:
     def generate(self, input_ids: torch.Tensor, pixel_values: torch.Tensor, n_tokens: int, graph: bool = True,
                  kv: torch.Tensor = None, do_sample: bool = False, temperature: float = 0.8, top_p: float = 0.9,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
-                 pad_token_id: Optional[int] = None, sync_every: int = 16, return_lengths: bool = False):
+                 pad_token_id: Optional[int] = None, sync_every: int = 16, return_lengths: bool = False,
+                 attention_mask: Optional[torch.Tensor] = None):
         """Batched generation: prefill, then n_tokens-1 decode steps
         with the next token picked on the device -- greedy argmax, or with do_sample the
         temperature + top-p draw of inference.py:64-66 -- and no host sync per token.
@@ -426,9 +477,19 @@ class Engine:
         The loop ends early once every row has stopped, checked every `sync_every` steps (one
         host read per check instead of the reference's `.item()` per token); the result is
         trimmed to the longest row.  return_lengths: also return int64 (B,) tokens per row up
-        to and including its eos (the length of the reference's generated_tokens)."""
+        to and including its eos (the length of the reference's generated_tokens).
+
+        attention_mask (B, L) of 0 / 1, optional: a batch of different prompts as the processor pads it
+        (padding="longest", left or right).  Each row then runs with its own length -- prefill over its
+        real tokens, decode at its own KV row and rotary position (pgmi_lm_forward_ragged /
+        pgmi_decode_ragged) -- and generates what it would alone.  No mask, or all ones: the lock-step
+        path.  kv defaults to new_kv(B, L + n_tokens + 1) either way."""
         ids = input_ids.to(self.device, torch.int64)
         B, L = ids.shape
+        if attention_mask is not None and R.lengths_from_mask(attention_mask) is not None:
+            return self._generate_ragged(ids, attention_mask, pixel_values, n_tokens, graph, kv, do_sample,
+                                         temperature, top_p, generator, eos_token_id, pad_token_id, sync_every,
+                                         return_lengths)
         if kv is None:
             kv = self.new_kv(B, L + n_tokens + 1)
         feats = self.project(self.vision(pixel_values))
@@ -475,6 +536,72 @@ class Engine:
             toks[:, t] = cur
         if not stop:
             return (toks, torch.full((B,), n_tokens, dtype=torch.int64, device=self.device)) if return_lengths else toks
+        toks = toks[:, :n_done]
+        hit = toks == int(eos_token_id)
+        first = torch.where(hit.any(1), hit.int().argmax(1) + 1, torch.full_like(hit[:, 0], n_done, dtype=torch.int64))
+        toks = toks[:, :int(first.max().item())].contiguous()
+        return (toks, first.to(torch.int64)) if return_lengths else toks
+
+    def _generate_ragged(self, ids, attention_mask, pixel_values, n_tokens, graph, kv, do_sample, temperature, top_p,
+                         generator, eos_token_id, pad_token_id, sync_every, return_lengths):
+        """generate() for a padded batch: the same three loops on the per-row step (decode_ragged)."""
+        ids, lens = R.right_pad(ids, attention_mask)
+        ids = ids.contiguous()
+        B, L = ids.shape
+        if kv is None:
+            kv = self.new_kv(B, L + n_tokens + 1)
+        feats = self.project(self.vision(pixel_values))
+        logits = self.lm_forward(kv, 0, torch.arange(L).expand(B, L), ids=ids, image_feats=feats, logits_rows=2,
+                                 lens=lens)
+        toks = torch.empty((B, n_tokens), dtype=torch.int64, device=self.device)
+        if do_sample:
+            us = torch.rand((n_tokens, B), device=self.device, generator=generator)
+            toks[:, 0] = self.sample_top_p(logits[:, 0], top_p, temperature, u=us[0])
+        else:
+            toks[:, 0] = self.argmax(logits[:, 0])
+        # per-B persistent buffers (step logits, fed-back ids, chunk record): stable pointers, so repeated
+        # generate calls on the same cache replay the decode graphs they captured
+        bufs = self._ragged_buf.get(B)
+        if bufs is None:
+            bufs = (torch.empty((B, self.cfgd["t_vocab"]), dtype=torch.float32, device=self.device),
+                    torch.empty(B, dtype=torch.int64, device=self.device),
+                    torch.empty(B, dtype=torch.int64, device=self.device),
+                    torch.empty((self.GEN_CHUNK, B), dtype=torch.int64, device=self.device))
+            self._ragged_buf[B] = bufs
+        step_logits, cur, nxt, rec = bufs
+        cur.copy_(toks[:, 0])
+        lens = lens.to(torch.int32)
+        stop = eos_token_id is not None
+        if stop:
+            pad = int(eos_token_id if pad_token_id is None else pad_token_id)
+            finished = torch.zeros(B, dtype=torch.int32, device=self.device)
+            alive = torch.empty(1, dtype=torch.int32, device=self.device)
+            self._eos_update(cur, finished, int(eos_token_id), pad, alive)
+            toks[:, 0] = cur
+        n_done = n_tokens
+        full = torch.full((B,), n_tokens, dtype=torch.int64, device=self.device)
+        if not do_sample and not stop and graph and n_tokens > 1 and B >= self.GEN_MIN_BATCH:
+            t = 1
+            while t < n_tokens:
+                n = min(self.GEN_CHUNK, n_tokens - t)
+                self.decode_ragged(cur, kv, lens + (t - 1), lens + t, n, logits=step_logits, tokens=rec, graph=graph)
+                toks[:, t:t + n] = rec[:n].t()
+                t += n
+            return (toks, full) if return_lengths else toks
+        for t in range(1, n_tokens):
+            if stop and (t - 1) % max(1, sync_every) == 0 and int(alive.item()) == 0:
+                n_done = t
+                break
+            if do_sample:
+                self.decode_ragged(cur, kv, lens + (t - 1), lens + t, logits=step_logits, next_ids=nxt, graph=graph)
+                cur.copy_(self.sample_top_p(step_logits, top_p, temperature, u=us[t]))
+            else:  # greedy: the argmax is fed back in place
+                self.decode_ragged(cur, kv, lens + (t - 1), lens + t, logits=step_logits, next_ids=cur, graph=graph)
+            if stop:
+                self._eos_update(cur, finished, int(eos_token_id), pad, alive)
+            toks[:, t] = cur
+        if not stop:
+            return (toks, full) if return_lengths else toks
         toks = toks[:, :n_done]
         hit = toks == int(eos_token_id)
         first = torch.where(hit.any(1), hit.int().argmax(1) + 1, torch.full_like(hit[:, 0], n_done, dtype=torch.int64))
