@@ -195,6 +195,13 @@ int pgmi_decode_embeds_dev(pgmi_ctx* ctx, const void* embeds, int B, void* kv, i
  * called again with identical pointer and size arguments (the graph is captured on the second
  * such call; a replay reads the same addresses as the eager call would).  0 = always eager. */
 int pgmi_set_prefill_graph(pgmi_ctx* ctx, int on);
+/* A context keeps two graph caches, the prefill's (pgmi_vision, pgmi_lm_forward*) and the decode steps' (every
+ * pgmi_decode* call with use_graph != 0), each keyed by the call's pointer and size arguments and each holding at
+ * most PGMI_GRAPH_CACHE_MAX keys: a call whose new key would exceed that drops its whole cache first (and, like any
+ * first call with a key, runs eagerly), so callers that pass fresh buffers every time cannot grow it.
+ * pgmi_graph_count: the keys a cache holds now (which 0 = prefill, 1 = decode), -1 for a null context. */
+#define PGMI_GRAPH_CACHE_MAX 64
+int pgmi_graph_count(const pgmi_ctx* ctx, int which);
 /* Batched decode (B >= 3, MFMA projections) RMSNorm form: 0 = each input norm computed once per row
  * and read unstaged by the q|k|v / gate|up projections (default), 1 = staged inside each projection,
  * -1 = back to the default.  Same arithmetic either way (bf16 normalised rows);

@@ -12,7 +12,6 @@
 #include <cstring>
 #include <map>
 #include <string>
-#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -54,28 +53,31 @@ struct Slot {
     int64_t numel;
 };
 
-struct GraphKey {
-    int B;
-    void* kv;
-    int kv_batch, kv_max;
-    float* logits;
-    int64_t* next;
-    const int64_t* ids;  // the ids buffer the graph reads (the context's staging copy, or in place)
-    bool emb;            // the step's input is the staged embedding rows (pgmi_decode_embeds), not ids
-    int masked;          // 0: no mask (a zero word), 1: staged bf16 mask (sum rounded), 2: staged fp32 mask
-    int n_steps;         // decode steps captured back to back (pgmi_decode_steps; 1 otherwise)
-    int64_t* tokens;     // their per-step token record ([n_steps][B], may be null)
-    bool ragged;         // per-row step records (pgmi_decode_ragged): never aliases a lock-step graph
-    bool operator<(const GraphKey& o) const {
-        return std::tie(B, kv, kv_batch, kv_max, logits, next, ids, emb, masked, n_steps, tokens, ragged) <
-               std::tie(o.B, o.kv, o.kv_batch, o.kv_max, o.logits, o.next, o.ids, o.emb, o.masked, o.n_steps,
-                        o.tokens, o.ragged);
+// Captured hipGraphs of one kind of call, keyed by every pointer and size the captured body reads (so a replay
+// is that call).  Bounded: see run_graphed.
+struct GraphCache {
+    std::map<std::vector<intptr_t>, hipGraphExec_t> map;  // null: the key was seen once (run eagerly), no graph yet
+    void clear() {
+        for (auto& kv : map)
+            if (kv.second) (void)hipGraphExecDestroy(kv.second);
+        map.clear();
     }
 };
 
-struct GraphEntry {
-    int seen = 0;
-    hipGraphExec_t exec = nullptr;
+// Weight pointers into the bound slab, resolved once by pgmi_bind_weights (bind_tables); fused projections
+// (q|k|v, gate|up) are named by their first tensor, the others follow it in the slab (build_layout).
+struct VisionLayerW {
+    const uint16_t *qkv_w, *qkv_b, *out_w, *out_b, *ln1_w, *ln1_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ln2_w, *ln2_b;
+};
+struct TextLayerW {
+    const uint16_t *qkv, *o, *gate_up, *down, *in_norm, *post_norm;
+    // batched decode (B >= 3): this layer's fragment-major images (ensure_mf_image), null while the image is absent
+    const uint16_t *mf_gate_up = nullptr, *mf_qkv = nullptr, *mf_o = nullptr, *mf_down = nullptr;
+};
+struct WeightTable {
+    const uint16_t *patch_conv_w, *patch_b, *pos_emb, *post_ln_w, *post_ln_b, *proj_w, *proj_b, *embed, *final_norm;
+    std::vector<VisionLayerW> v;
+    std::vector<TextLayerW> t;
 };
 
 struct pgmi_ctx {
@@ -85,6 +87,7 @@ struct pgmi_ctx {
     std::unordered_map<std::string, int> index;
     int64_t slab_bytes = 0;
     uint8_t* slab = nullptr;
+    WeightTable w;
     std::vector<float> inv_freq;
     std::vector<uint16_t> host_cos, host_sin;  // optional exact table
     bool prepared = false;
@@ -108,9 +111,8 @@ struct pgmi_ctx {
     uint16_t* dHn;  // batched decode (B >= 3): the RMSNorm'd rows the unstaged MFMA projections read
     float* dSS;     // batched decode: o_proj's 16-column partial sums of squares of h, [B][H / 16]
     // batched decode (max_batch >= 3): fragment-major images of every layer's gate|up, q|k|v (in the GEMV's row
-    // order), o_proj and down weights (mf_swizzle), [layer][gate|up 2 I x H | q|k|v QKVN x H | o_proj | down H x I]
+    // order), o_proj and down weights (mf_swizzle); laid out by ensure_mf_image, read through w.t[i].mf_*
     uint16_t* mfw = nullptr;
-    size_t mfw_layer = 0;
     bool mfw_dirty = false;  // the fragment-major images are (re)built by the next batched decode step
     float *opart, *pmax, *dlogits, *amax_v;
     int *pidx, *amax_i;
@@ -126,10 +128,10 @@ struct pgmi_ctx {
     int64_t* d_next;             // argmax target when the caller passes none
     unsigned* lm_done;           // lm_head arrival counter (argmax folded into its last workgroup)
     hipStream_t cap_stream = nullptr;
-    std::map<GraphKey, GraphEntry> graphs;
-    // prefill graphs (vision tower, language-model forward): replayed for repeated calls with
-    // identical pointer/shape arguments (a replay is the eager call: kernels read the same
-    // addresses at run time), captured on the second such call
+    // prefill graphs (vision tower, language-model forward) and decode graphs (the captured steps): replayed
+    // for repeated calls with identical pointer/shape arguments (a replay is the eager call: kernels read the
+    // same addresses at run time), captured on the second such call (run_graphed)
+    GraphCache pgraphs, dgraphs;
     bool prefill_graph = true;
     int mf_staged = -1;  // batched decode RMSNorm form (mf_staged()); -1 = default (unstaged)
     // device step state as the last enqueued per-phase decode step leaves it (advanced in-graph)
@@ -139,7 +141,6 @@ struct pgmi_ctx {
     bool rstep_known = false;
     int rstep_B = 0;
     int rstep_kv[8] = {0}, rstep_pos[8] = {0};
-    std::map<std::vector<intptr_t>, GraphEntry> pgraphs;
     // in-situ timing probe of the prefill MLP GEMMs (pgmi_prefill_probe): events around layer i's gate|up
     // GEMM (ev[4i], ev[4i+1]) and down GEMM (ev[4i+2], ev[4i+3]) of eager forwards
     std::vector<hipEvent_t> probe_ev;
@@ -148,19 +149,6 @@ struct pgmi_ctx {
 };
 
 namespace {
-
-void clear_pgraphs(pgmi_ctx* x) {
-    for (auto& kv : x->pgraphs)
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-    x->pgraphs.clear();
-}
-
-// the captured decode steps
-void clear_dgraphs(pgmi_ctx* x) {
-    for (auto& kv : x->graphs)
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-    x->graphs.clear();
-}
 
 int n_img(const pgmi_config& c) { return (c.v_image / c.v_patch) * (c.v_image / c.v_patch); }
 
@@ -223,17 +211,51 @@ void build_layout(pgmi_ctx* x) {
     add_slot(x, "language_model.model.norm.weight", {H});
 }
 
-inline uint16_t* W(pgmi_ctx* x, const std::string& name) {
-    auto it = x->index.find(name);
-    if (it == x->index.end()) return nullptr;
-    return reinterpret_cast<uint16_t*>(x->slab + x->slots[it->second].off);
-}
-
-inline uint16_t* VL(pgmi_ctx* x, int i, const char* suffix) {
-    return W(x, "vision_tower.vision_model.encoder.layers." + std::to_string(i) + "." + suffix);
-}
-inline uint16_t* TL(pgmi_ctx* x, int i, const char* suffix) {
-    return W(x, "language_model.model.layers." + std::to_string(i) + "." + suffix);
+// Resolve every weight the forward passes read, once per bound slab: a name without a slot is an error here,
+// not a null kernel argument later.
+int bind_tables(pgmi_ctx* x) {
+    std::string missing;
+    auto W = [&](const std::string& name) -> const uint16_t* {
+        auto it = x->index.find(name);
+        if (it == x->index.end()) {
+            if (missing.empty()) missing = name;
+            return nullptr;
+        }
+        return reinterpret_cast<const uint16_t*>(x->slab + x->slots[it->second].off);
+    };
+    WeightTable& w = x->w;
+    const std::string vp = "vision_tower.vision_model.", tp = "language_model.model.";
+    w.patch_conv_w = W(vp + "embeddings.patch_embedding.weight");
+    w.patch_b = W(vp + "embeddings.patch_embedding.bias");
+    w.pos_emb = W(vp + "embeddings.position_embedding.weight");
+    w.post_ln_w = W(vp + "post_layernorm.weight");
+    w.post_ln_b = W(vp + "post_layernorm.bias");
+    w.proj_w = W("multi_modal_projector.linear.weight");
+    w.proj_b = W("multi_modal_projector.linear.bias");
+    w.embed = W(tp + "embed_tokens.weight");
+    w.final_norm = W(tp + "norm.weight");
+    w.v.resize(x->c.v_layers);
+    for (int i = 0; i < x->c.v_layers; ++i) {
+        const std::string lp = vp + "encoder.layers." + std::to_string(i) + ".";
+        w.v[i] = {W(lp + "self_attn.q_proj.weight"), W(lp + "self_attn.q_proj.bias"),  // q|k|v adjacent
+                  W(lp + "self_attn.out_proj.weight"), W(lp + "self_attn.out_proj.bias"),
+                  W(lp + "layer_norm1.weight"), W(lp + "layer_norm1.bias"), W(lp + "mlp.fc1.weight"),
+                  W(lp + "mlp.fc1.bias"), W(lp + "mlp.fc2.weight"), W(lp + "mlp.fc2.bias"),
+                  W(lp + "layer_norm2.weight"), W(lp + "layer_norm2.bias")};
+    }
+    w.t.resize(x->c.t_layers);  // (keeps a built fragment-major image's pointers)
+    for (int i = 0; i < x->c.t_layers; ++i) {
+        const std::string lp = tp + "layers." + std::to_string(i) + ".";
+        TextLayerW& t = w.t[i];
+        t.qkv = W(lp + "self_attn.q_proj.weight");  // q|k|v adjacent
+        t.o = W(lp + "self_attn.o_proj.weight");
+        t.gate_up = W(lp + "mlp.gate_proj.weight");  // gate rows, then up rows
+        t.down = W(lp + "mlp.down_proj.weight");
+        t.in_norm = W(lp + "input_layernorm.weight");
+        t.post_norm = W(lp + "post_attention_layernorm.weight");
+    }
+    if (!missing.empty()) return fail(PGMI_E_STATE, "weight layout has no tensor named " + missing);
+    return 0;
 }
 
 uint16_t host_f2bf(float f) {
@@ -301,6 +323,54 @@ int ensure_prepared(pgmi_ctx* x) {
     if (!x->prepared) return fail(PGMI_E_STATE, "pgmi_prepare() has not been called");
     if (!x->slab) return fail(PGMI_E_STATE, "weights are not bound (pgmi_bind_weights)");
     return 0;
+}
+
+// The one graph policy: the first call with a key runs body(s) eagerly (kernel attributes are set on first launch),
+// the second captures body(cap_stream), instantiates and launches, later ones replay.  A key that would be entry
+// PGMI_GRAPH_CACHE_MAX + 1 drops the whole cache first (fresh buffers every call must not grow it without bound).
+// sync_before_capture: the decode step's hipStreamSynchronize(s); the prefill has none (pgmi_vision may be called
+// where a synchronise is not allowed).
+template <class F>
+int run_graphed(pgmi_ctx* x, GraphCache& gc, hipStream_t s, const std::vector<intptr_t>& key, F body,
+                bool sync_before_capture) {
+    auto it = gc.map.find(key);
+    if (it == gc.map.end()) {
+        if (gc.map.size() >= PGMI_GRAPH_CACHE_MAX) gc.clear();
+        gc.map[key] = nullptr;
+        return body(s);
+    }
+    if (it->second) {
+        HIPCHK(hipGraphLaunch(it->second, s));
+        return 0;
+    }
+    // Capture.  Whatever fails from here on: an opened capture is ended, a graph we got is destroyed and the key's
+    // entry is erased (the next call with it starts over, eagerly); the first error is the one reported.
+    hipGraph_t g = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int rc = 0;
+    hipError_t e = sync_before_capture ? hipStreamSynchronize(s) : hipSuccess;
+    if (e == hipSuccess && (e = hipStreamBeginCapture(x->cap_stream, hipStreamCaptureModeThreadLocal)) == hipSuccess) {
+        rc = body(x->cap_stream);  // may fail and return (HIPCHK) with the capture open: it is ended here
+        const hipError_t end = hipStreamEndCapture(x->cap_stream, &g);
+        if (rc == 0) e = end;
+    }
+    if (rc == 0 && e == hipSuccess) e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    if (g) (void)hipGraphDestroy(g);
+    if (rc == 0 && e == hipSuccess) e = hipGraphLaunch(exec, s);
+    if (rc == 0 && e == hipSuccess) {
+        gc.map[key] = exec;
+        return 0;
+    }
+    if (exec) (void)hipGraphExecDestroy(exec);
+    gc.map.erase(key);
+    return rc ? rc : fail(PGMI_E_HIP, std::string("hipGraph capture: ") + hipGetErrorString(e));
+}
+
+// prefill calls (vision tower, language-model forward): one body, and no graph at all while prefill_graph is off
+template <class F>
+int run_prefill(pgmi_ctx* x, hipStream_t s, const std::vector<intptr_t>& key, F body) {
+    if (!x->prefill_graph) return body(s);
+    return run_graphed(x, x->pgraphs, s, key, body, false);
 }
 
 }  // namespace
@@ -374,11 +444,10 @@ int pgmi_create(int device, const pgmi_config* cfg, pgmi_ctx** out) {
 }
 
 int pgmi_destroy(pgmi_ctx* x) {
-    if (x)
-        for (auto& e : x->probe_ev) (void)hipEventDestroy(e);
     if (!x) return 0;
-    clear_dgraphs(x);
-    clear_pgraphs(x);
+    for (auto& e : x->probe_ev) (void)hipEventDestroy(e);
+    x->dgraphs.clear();
+    x->pgraphs.clear();
     for (void* p : x->allocs) (void)hipFree(p);
     if (x->cap_stream) (void)hipStreamDestroy(x->cap_stream);
     delete x;
@@ -402,9 +471,9 @@ int pgmi_bind_weights(pgmi_ctx* x, void* slab) {
     if (!x || !slab) return fail(PGMI_E_ARG, "null argument");
     if (reinterpret_cast<uintptr_t>(slab) % 256 != 0) return fail(PGMI_E_ARG, "weight slab must be 256-byte aligned");
     x->slab = reinterpret_cast<uint8_t*>(slab);
-    clear_dgraphs(x);
-    clear_pgraphs(x);
-    return 0;
+    x->dgraphs.clear();
+    x->pgraphs.clear();
+    return bind_tables(x);
 }
 
 int pgmi_load_weight(pgmi_ctx* x, const char* name, const void* src, int dtype, int on_device, void* stream) {
@@ -639,8 +708,7 @@ int pgmi_prepare(pgmi_ctx* x) {
         HIPCHK(hipStreamCreateWithFlags(&x->cap_stream, hipStreamNonBlocking));
     }
     // derived tensors
-    pad_rows(nullptr, W(x, "vision_tower.vision_model.embeddings.patch_embedding.weight"), c.v_hidden,
-             c.v_channels * c.v_patch * c.v_patch, x->kpad, x->patch_w);
+    pad_rows(nullptr, x->w.patch_conv_w, c.v_hidden, c.v_channels * c.v_patch * c.v_patch, x->kpad, x->patch_w);
     LAUNCHCHK();
     // the batched decode's fragment-major weight images: built by the first decode step with B >= 3 after this
     // call (ensure_mf_image), not here -- a context that never decodes a batch (the drop-in's single-sequence
@@ -656,8 +724,8 @@ int pgmi_prepare(pgmi_ctx* x) {
     HIPCHK(hipMemcpy(x->cosT, cs.data(), cs.size() * 2, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(x->sinT, sn.data(), sn.size() * 2, hipMemcpyHostToDevice));
     HIPCHK(hipDeviceSynchronize());
-    clear_dgraphs(x);
-    clear_pgraphs(x);
+    x->dgraphs.clear();
+    x->pgraphs.clear();
     x->prepared = true;
     return 0;
 }
@@ -667,38 +735,10 @@ int64_t pgmi_kv_bytes(const pgmi_ctx* x, int batch, int max_tokens) {
     return (int64_t)x->c.t_layers * 2 * batch * max_tokens * x->c.t_kv_heads * x->c.t_head_dim * 2;
 }
 
-// Run body(stream) eagerly, or replay its captured hipGraph: the first call with a given key
-// runs eagerly (kernel attributes are set on first launch), the second captures, later ones
-// replay.  The key holds every pointer and size the body reads, so a replay is that call.
-extern "C++" {
-template <class F>
-static int run_graphed(pgmi_ctx* x, hipStream_t s, const std::vector<intptr_t>& key, F body) {
-    if (!x->prefill_graph) return body(s);
-    GraphEntry& ge = x->pgraphs[key];
-    if (!ge.exec) {
-        if (ge.seen++ == 0) return body(s);
-        if (x->pgraphs.size() > 64) {  // bound the cache (e.g. fresh buffers every call)
-            clear_pgraphs(x);
-            return body(s);
-        }
-        hipGraph_t g;
-        HIPCHK(hipStreamBeginCapture(x->cap_stream, hipStreamCaptureModeThreadLocal));
-        const int rc = body(x->cap_stream);
-        HIPCHK(hipStreamEndCapture(x->cap_stream, &g));
-        if (rc) {
-            (void)hipGraphDestroy(g);
-            return rc;
-        }
-        GraphEntry& ge2 = x->pgraphs[key];
-        HIPCHK(hipGraphInstantiate(&ge2.exec, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-        HIPCHK(hipGraphLaunch(ge2.exec, s));
-        return 0;
-    }
-    HIPCHK(hipGraphLaunch(ge.exec, s));
-    return 0;
+int pgmi_graph_count(const pgmi_ctx* x, int which) {
+    if (!x) return -1;
+    return (int)(which == 0 ? x->pgraphs : x->dgraphs).map.size();
 }
-}  // extern "C++"
 
 static int vision_body(pgmi_ctx* x, hipStream_t s, const void* pixels, int dtype, int B, void* feats);
 
@@ -709,7 +749,7 @@ int pgmi_vision(pgmi_ctx* x, const void* pixels, int dtype, int B, void* feats, 
     if (B < 1 || B > c.max_batch) return fail(PGMI_E_ARG, "batch exceeds max_batch");
     if (!pixels || !feats) return fail(PGMI_E_ARG, "null argument");
     const std::vector<intptr_t> key{1, (intptr_t)pixels, dtype, B, (intptr_t)feats};
-    rc = run_graphed(x, (hipStream_t)stream, key,
+    rc = run_prefill(x, (hipStream_t)stream, key,
                      [&](hipStream_t st) { return vision_body(x, st, pixels, dtype, B, feats); });
     if (rc) return rc;
     LAUNCHCHK();
@@ -718,13 +758,14 @@ int pgmi_vision(pgmi_ctx* x, const void* pixels, int dtype, int B, void* feats, 
 
 static int vision_body(pgmi_ctx* x, hipStream_t s, const void* pixels, int dtype, int B, void* feats) {
     const pgmi_config& c = x->c;
+    const WeightTable& w = x->w;
     const int N = n_img(c), D = c.v_hidden, Iv = c.v_intermediate, rows = B * N;
     const float eps = c.v_ln_eps;
     patchify(s, pixels, dtype == PGMI_DTYPE_F32, B, c.v_channels, c.v_image, c.v_image, c.v_patch, x->kpad, x->vP);
     // Conv2d + bias + position embedding (modeling_siglip.py:67,76)
     EpiArgs e{};
-    e.bias = W(x, "vision_tower.vision_model.embeddings.patch_embedding.bias");
-    e.pos = W(x, "vision_tower.vision_model.embeddings.position_embedding.weight");
+    e.bias = w.patch_b;
+    e.pos = w.pos_emb;
     e.npos = N;
     e.out = x->vX;
     e.ldo = D;
@@ -732,14 +773,15 @@ static int vision_body(pgmi_ctx* x, hipStream_t s, const void* pixels, int dtype
     const float scale = (float)std::pow((double)(D / c.v_heads), -0.5);  // head_dim**-0.5 (:89)
     // LayerNorm1 of layer 0; every later LayerNorm is fused with the preceding projection's
     // split-K reduction + bias + residual (splitk_res_norm)
-    layernorm(s, x->vX, VL(x, 0, "layer_norm1.weight"), VL(x, 0, "layer_norm1.bias"), eps, x->vT, rows, D);
+    if (c.v_layers > 0) layernorm(s, x->vX, w.v[0].ln1_w, w.v[0].ln1_b, eps, x->vT, rows, D);
     for (int i = 0; i < c.v_layers; ++i) {
         const bool last = i + 1 == c.v_layers;
+        const VisionLayerW& l = w.v[i];
         EpiArgs q{};
-        q.bias = VL(x, i, "self_attn.q_proj.bias");  // q|k|v biases adjacent
+        q.bias = l.qkv_b;
         q.out = x->vQKV;
         q.ldo = 3 * D;
-        gemm(s, x->vT, D, VL(x, i, "self_attn.q_proj.weight"), D, rows, 3 * D, D, EPI_BIAS, q, x->ws, x->ws_bytes);
+        gemm(s, x->vT, D, l.qkv_w, D, rows, 3 * D, D, EPI_BIAS, q, x->ws, x->ws_bytes);
         AttnArgs a{};
         a.q = x->vQKV; a.q_b_stride = (long)N * 3 * D; a.q_row_stride = 3 * D; a.q_head_stride = 72;
         a.k = x->vQKV + D; a.k_b_stride = a.q_b_stride; a.k_row_stride = 3 * D; a.k_head_stride = 72;
@@ -749,27 +791,22 @@ static int vision_body(pgmi_ctx* x, hipStream_t s, const void* pixels, int dtype
         a.ws = x->ws; a.ws_floats = (long)(x->ws_bytes / sizeof(float));
         attention_prefill(s, 72, a);
         EpiArgs o{};
-        o.bias = VL(x, i, "self_attn.out_proj.bias");
+        o.bias = l.out_b;
         o.res = x->vX; o.ldr = D; o.out = x->vX; o.ldo = D;
-        const int spo = gemm(s, x->vAO, D, VL(x, i, "self_attn.out_proj.weight"), D, rows, D, D, EPI_BIAS_RES, o, x->ws,
-                             x->ws_bytes, 0, true);
-        splitk_res_norm(s, x->ws, spo, o.bias, x->vX, VL(x, i, "layer_norm2.weight"), VL(x, i, "layer_norm2.bias"),
-                        eps, x->vT, rows, D);
+        const int spo = gemm(s, x->vAO, D, l.out_w, D, rows, D, D, EPI_BIAS_RES, o, x->ws, x->ws_bytes, 0, true);
+        splitk_res_norm(s, x->ws, spo, o.bias, x->vX, l.ln2_w, l.ln2_b, eps, x->vT, rows, D);
         EpiArgs f1{};
-        f1.bias = VL(x, i, "mlp.fc1.bias"); f1.out = x->vH; f1.ldo = Iv;
-        gemm(s, x->vT, D, VL(x, i, "mlp.fc1.weight"), D, rows, Iv, D, EPI_BIAS_GELU, f1, x->ws, x->ws_bytes);
+        f1.bias = l.fc1_b; f1.out = x->vH; f1.ldo = Iv;
+        gemm(s, x->vT, D, l.fc1_w, D, rows, Iv, D, EPI_BIAS_GELU, f1, x->ws, x->ws_bytes);
         EpiArgs f2{};
-        f2.bias = VL(x, i, "mlp.fc2.bias"); f2.res = x->vX; f2.ldr = D; f2.out = x->vX; f2.ldo = D;
-        const int sp = gemm(s, x->vH, Iv, VL(x, i, "mlp.fc2.weight"), Iv, rows, D, Iv, EPI_BIAS_RES, f2, x->ws,
-                            x->ws_bytes, 0, true);
-        splitk_res_norm(s, x->ws, sp, f2.bias, x->vX,
-                        last ? W(x, "vision_tower.vision_model.post_layernorm.weight") : VL(x, i + 1, "layer_norm1.weight"),
-                        last ? W(x, "vision_tower.vision_model.post_layernorm.bias") : VL(x, i + 1, "layer_norm1.bias"),
-                        eps, last ? reinterpret_cast<uint16_t*>(feats) : x->vT, rows, D);
+        f2.bias = l.fc2_b; f2.res = x->vX; f2.ldr = D; f2.out = x->vX; f2.ldo = D;
+        const int sp = gemm(s, x->vH, Iv, l.fc2_w, Iv, rows, D, Iv, EPI_BIAS_RES, f2, x->ws, x->ws_bytes, 0, true);
+        splitk_res_norm(s, x->ws, sp, f2.bias, x->vX, last ? w.post_ln_w : w.v[i + 1].ln1_w,
+                        last ? w.post_ln_b : w.v[i + 1].ln1_b, eps, last ? reinterpret_cast<uint16_t*>(feats) : x->vT,
+                        rows, D);
     }
     if (c.v_layers == 0)
-        layernorm(s, x->vX, W(x, "vision_tower.vision_model.post_layernorm.weight"),
-                  W(x, "vision_tower.vision_model.post_layernorm.bias"), eps, reinterpret_cast<uint16_t*>(feats), rows, D);
+        layernorm(s, x->vX, w.post_ln_w, w.post_ln_b, eps, reinterpret_cast<uint16_t*>(feats), rows, D);
     LAUNCHCHK();
     return 0;
 }
@@ -780,12 +817,11 @@ int pgmi_project(pgmi_ctx* x, const void* feats, int rows, void* out, void* stre
     if (!feats || !out || rows < 1) return fail(PGMI_E_ARG, "bad argument");
     if (rows > x->c.max_batch * n_img(x->c)) return fail(PGMI_E_ARG, "rows exceed workspace capacity");
     EpiArgs e{};
-    e.bias = W(x, "multi_modal_projector.linear.bias");
+    e.bias = x->w.proj_b;
     e.out = reinterpret_cast<uint16_t*>(out);
     e.ldo = x->c.projection_dim;
-    gemm((hipStream_t)stream, reinterpret_cast<const uint16_t*>(feats), x->c.v_hidden,
-         W(x, "multi_modal_projector.linear.weight"), x->c.v_hidden, rows, x->c.projection_dim, x->c.v_hidden,
-         EPI_BIAS, e, x->ws, x->ws_bytes);
+    gemm((hipStream_t)stream, reinterpret_cast<const uint16_t*>(feats), x->c.v_hidden, x->w.proj_w, x->c.v_hidden, rows,
+         x->c.projection_dim, x->c.v_hidden, EPI_BIAS, e, x->ws, x->ws_bytes);
     LAUNCHCHK();
     return 0;
 }
@@ -795,8 +831,8 @@ int pgmi_embed(pgmi_ctx* x, const int64_t* ids, int rows, void* out, void* strea
     if ((rc = ensure_prepared(x))) return rc;
     if (!ids || !out) return fail(PGMI_E_ARG, "null argument");
     // plain lookup: normalizer 1, no pad zeroing (nn.Embedding, modeling_gemma.py:565)
-    embed_rows((hipStream_t)stream, ids, rows, W(x, "language_model.model.embed_tokens.weight"), x->c.t_hidden,
-               1.0f, INT64_MIN, reinterpret_cast<uint16_t*>(out));
+    embed_rows((hipStream_t)stream, ids, rows, x->w.embed, x->c.t_hidden, 1.0f, INT64_MIN,
+               reinterpret_cast<uint16_t*>(out));
     LAUNCHCHK();
     return 0;
 }
@@ -856,7 +892,7 @@ static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, 
     const std::vector<intptr_t> key{2, (intptr_t)ids, (intptr_t)image_feats, n_img_rows, (intptr_t)embeds, B, L,
                                     (intptr_t)kv, kv_batch, kv_max, kv_start, (intptr_t)logits, logits_rows,
                                     (intptr_t)ragged};
-    rc = run_graphed(x, (hipStream_t)stream, key, [&](hipStream_t st) {
+    rc = run_prefill(x, (hipStream_t)stream, key, [&](hipStream_t st) {
         return lm_body(x, st, ids, image_feats, n_img_rows, embeds, B, L, kv, kv_batch, kv_max, kv_start, logits,
                        logits_rows, ragged);
     });
@@ -877,7 +913,7 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
     const int QKVN = (NH + 2 * NKV) * HD;
     const float eps = c.t_rms_eps;
     const float normalizer = bf16_round_host(std::sqrt((float)H));  // torch.tensor(H**0.5, dtype=bf16) (:367)
-    const uint16_t* E = W(x, "language_model.model.embed_tokens.weight");
+    const uint16_t* E = x->w.embed;
     if (embeds) {
         scale_rows(s, reinterpret_cast<const uint16_t*>(embeds), (long)R * H, normalizer, x->Hs);
     } else {
@@ -887,12 +923,13 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
     }
     const long kvd = (long)NKV * HD, kvb = (long)kv_max * kvd;
     uint16_t* kvp = reinterpret_cast<uint16_t*>(kv);
-    const uint16_t* fnorm = W(x, "language_model.model.norm.weight");
+    const uint16_t* fnorm = x->w.final_norm;
     const bool last_only = logits_rows == 2 && L > 1 && c.t_layers > 0;
     // input RMSNorm of layer 0; every later RMSNorm (and the final norm) is fused with the
     // preceding projection's split-K reduction + residual (splitk_res_norm)
-    rmsnorm(s, x->Hs, c.t_layers ? TL(x, 0, "input_layernorm.weight") : fnorm, eps, x->Tn, R, H);
+    rmsnorm(s, x->Hs, c.t_layers ? x->w.t[0].in_norm : fnorm, eps, x->Tn, R, H);
     for (int i = 0; i < c.t_layers; ++i) {
+        const TextLayerW& w = x->w.t[i];
         uint16_t* Kc = kvp + ((long)(i * 2 + 0) * kv_batch) * kvb;
         uint16_t* Vc = kvp + ((long)(i * 2 + 1) * kv_batch) * kvb;
         EpiArgs q{};
@@ -901,9 +938,8 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
         q.rpos = x->dpos; q.cosT = x->cosT; q.sinT = x->sinT; q.max_pos = c.t_max_pos;
         q.q_out = x->Qr; q.kc = Kc; q.vc = Vc; q.kv_b_stride = kvb; q.kv_start = kv_start;
         q.L = L; q.nh = NH; q.nkv = NKV;
-        const uint16_t* Wqkv = TL(x, i, "self_attn.q_proj.weight");
-        if (HD != 256 || !gemm_qkv_rope(s, x->Tn, H, Wqkv, H, R, QKVN, H, q)) {
-            int sp = gemm(s, x->Tn, H, Wqkv, H, R, QKVN, H, EPI_STORE, q, x->ws, x->ws_bytes, 0, true);
+        if (HD != 256 || !gemm_qkv_rope(s, x->Tn, H, w.qkv, H, R, QKVN, H, q)) {
+            int sp = gemm(s, x->Tn, H, w.qkv, H, R, QKVN, H, EPI_STORE, q, x->ws, x->ws_bytes, 0, true);
             rope_kv_append(s, x->QKV, x->ws, sp, B, L, NH, NKV, x->dpos, x->cosT, x->sinT, c.t_max_pos, x->Qr, Kc, Vc,
                            kvb, kv_start);
         }
@@ -936,39 +972,34 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
                 HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&x->pstep->kv_len), kv_start + L - 1, 1, s));
                 a.mask = x->d_zero; a.mask_b_stride = 0; a.mask_k_stride = 0; a.mask_round = 1;
                 attention_decode(s, a, x->pstep, kv_start + L, x->opart, x->max_chunks);
-                gemv_o_attn(s, B, NH, x->opart, x->max_chunks, x->pstep, TL(x, i, "self_attn.o_proj.weight"), H,
-                            x->lastrows, B >= gemv_mf_min_batch() ? x->dAO : nullptr);
+                gemv_o_attn(s, B, NH, x->opart, x->max_chunks, x->pstep, w.o, H, x->lastrows,
+                            B >= gemv_mf_min_batch() ? x->dAO : nullptr);
             } else {
                 attention_prefill(s, 256, a);
-                gemv_res(s, B, NH * HD, x->dAO, TL(x, i, "self_attn.o_proj.weight"), H, x->lastrows, x->ws);
+                gemv_res(s, B, NH * HD, x->dAO, w.o, H, x->lastrows, x->ws);
             }
-            gemv_geglu(s, B, x->lastrows, TL(x, i, "post_attention_layernorm.weight"), eps,
-                       TL(x, i, "mlp.gate_proj.weight"), c.t_intermediate, x->dACT);
-            gemv_res(s, B, c.t_intermediate, x->dACT, TL(x, i, "mlp.down_proj.weight"), H, x->lastrows, x->ws);
+            gemv_geglu(s, B, x->lastrows, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT);
+            gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->lastrows, x->ws);
             break;
         }
         attention_prefill(s, 256, a);
         EpiArgs o{};
         o.res = x->Hs; o.ldr = H; o.out = x->Hs; o.ldo = H;
-        int sp = gemm(s, x->AO, H, TL(x, i, "self_attn.o_proj.weight"), H, R, H, NH * HD, EPI_RES, o, x->ws, x->ws_bytes,
-                  0, true);
-        splitk_res_norm(s, x->ws, sp, nullptr, x->Hs, TL(x, i, "post_attention_layernorm.weight"), nullptr, eps, x->Tn,
-                        R, H);
+        int sp = gemm(s, x->AO, H, w.o, H, R, H, NH * HD, EPI_RES, o, x->ws, x->ws_bytes, 0, true);
+        splitk_res_norm(s, x->ws, sp, nullptr, x->Hs, w.post_norm, nullptr, eps, x->Tn, R, H);
         EpiArgs g{};
         g.out = x->ACT; g.ldo = c.t_intermediate;
         const bool probe = x->probe_on && (size_t)(4 * i + 3) < x->probe_ev.size();
         // probe: the GEMM kernel itself carries the events (its own start / end, gemm_probe_events)
         if (probe) gemm_probe_events(x->probe_ev[4 * i], x->probe_ev[4 * i + 1]);
-        gemm(s, x->Tn, H, TL(x, i, "mlp.gate_proj.weight"), H, R, c.t_intermediate, H, EPI_GEGLU, g, x->ws,
-             x->ws_bytes, c.t_intermediate);
+        gemm(s, x->Tn, H, w.gate_up, H, R, c.t_intermediate, H, EPI_GEGLU, g, x->ws, x->ws_bytes, c.t_intermediate);
         EpiArgs d{};
         d.res = x->Hs; d.ldr = H; d.out = x->Hs; d.ldo = H;
         if (probe) gemm_probe_events(x->probe_ev[4 * i + 2], x->probe_ev[4 * i + 3]);
-        sp = gemm(s, x->ACT, c.t_intermediate, TL(x, i, "mlp.down_proj.weight"), c.t_intermediate, R, H,
-                  c.t_intermediate, EPI_RES, d, x->ws, x->ws_bytes, 0, true);
+        sp = gemm(s, x->ACT, c.t_intermediate, w.down, c.t_intermediate, R, H, c.t_intermediate, EPI_RES, d, x->ws,
+                  x->ws_bytes, 0, true);
         const bool last = i + 1 == c.t_layers;
-        splitk_res_norm(s, x->ws, sp, nullptr, x->Hs, last ? fnorm : TL(x, i + 1, "input_layernorm.weight"), nullptr,
-                        eps, x->Tn, R, H);
+        splitk_res_norm(s, x->ws, sp, nullptr, x->Hs, last ? fnorm : x->w.t[i + 1].in_norm, nullptr, eps, x->Tn, R, H);
     }
     if (logits_rows == 0) {
         EpiArgs l{};  // Tn holds the final RMSNorm (modeling_gemma.py:379)
@@ -1007,7 +1038,7 @@ static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, vo
     const int H = c.t_hidden, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
     const float eps = c.t_rms_eps;
     const float normalizer = bf16_round_host(std::sqrt((float)H));
-    const uint16_t* E = W(x, "language_model.model.embed_tokens.weight");
+    const uint16_t* E = x->w.embed;
     const long kvd = (long)NKV * HD, kvb = (long)kv_max * kvd;
     uint16_t* kvp = reinterpret_cast<uint16_t*>(kv);
     // B <= 2: the embedding row is read by layer 0's q|k|v GEMV itself (one launch fewer per step)
@@ -1023,16 +1054,14 @@ static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, vo
     // 5.97 -> 7.59 us for a combine no shorter, 4.63 -> 4.72 us; with the combine inside the down launch,
     // B = 8 step 1.437 -> 1.446-1.465 ms, same box.)
     const bool mf = B >= gemv_mf_min_batch() && !mf_staged(x);
-    if (mf && c.t_layers > 0) rows_norm(s, x->dH, TL(x, 0, "input_layernorm.weight"), eps, B, H, x->dHn);
+    if (mf && c.t_layers > 0) rows_norm(s, x->dH, x->w.t[0].in_norm, eps, B, H, x->dHn);
     for (int i = 0; i < c.t_layers; ++i) {
         uint16_t* Kc = kvp + ((long)(i * 2 + 0) * kv_batch) * kvb;
         uint16_t* Vc = kvp + ((long)(i * 2 + 1) * kv_batch) * kvb;
-        // fragment-major weight images of this layer (prepare's mf_swizzle), when built: gate|up, q|k|v, o_proj
-        const uint16_t* Lf = x->mfw ? x->mfw + x->mfw_layer * i : nullptr;
-        const size_t gu_n = (size_t)2 * c.t_intermediate * H, qkv_n = (size_t)(NH + 2 * NKV) * HD * H;
-        gemv_qkv(s, B, NH, NKV, mf ? x->dHn : x->dH, mf ? nullptr : TL(x, i, "input_layernorm.weight"), eps,
-                 TL(x, i, "self_attn.q_proj.weight"), x->cosT, x->sinT, c.t_max_pos, st, x->dQ, Kc, Vc, kvb, x->ws,
-                 (fold && i == 0) ? &emb : nullptr, Lf ? Lf + gu_n : nullptr, sts);
+        // w.mf_*: the fragment-major images of this layer's weights (ensure_mf_image), null until built
+        const TextLayerW& w = x->w.t[i];
+        gemv_qkv(s, B, NH, NKV, mf ? x->dHn : x->dH, mf ? nullptr : w.in_norm, eps, w.qkv, x->cosT, x->sinT,
+                 c.t_max_pos, st, x->dQ, Kc, Vc, kvb, x->ws, (fold && i == 0) ? &emb : nullptr, w.mf_qkv, sts);
         AttnArgs a{};
         a.q = x->dQ; a.q_b_stride = (long)NH * HD; a.q_row_stride = NH * HD; a.q_head_stride = HD;
         a.k = Kc; a.k_b_stride = kvb; a.k_row_stride = (int)kvd; a.k_head_stride = HD;
@@ -1045,29 +1074,25 @@ static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, vo
             a.mask = x->d_zero; a.mask_b_stride = 0; a.mask_k_stride = 0; a.mask_round = 1;
         }
         attention_decode(s, a, st, launch_keys, x->opart, x->max_chunks, sts);
-        gemv_o_attn(s, B, NH, x->opart, x->max_chunks, st, TL(x, i, "self_attn.o_proj.weight"), H, x->dH,
-                    B >= gemv_mf_min_batch() ? x->dAO : nullptr, mf ? x->dSS : nullptr, Lf ? Lf + gu_n + qkv_n : nullptr,
-                    sts);
+        gemv_o_attn(s, B, NH, x->opart, x->max_chunks, st, w.o, H, x->dH, B >= gemv_mf_min_batch() ? x->dAO : nullptr,
+                    mf ? x->dSS : nullptr, w.mf_o, sts);
         if (mf) {
             // the post-attention RMSNorm: its sums of squares come from o_proj's epilogue (dSS), gate|up
             // normalises h on load (no k_rows_norm pass: B = 8 step -5 us per layer)
-            gemv_geglu(s, B, x->dH, TL(x, i, "post_attention_layernorm.weight"), eps, TL(x, i, "mlp.gate_proj.weight"),
-                       c.t_intermediate, x->dACT, x->dSS, Lf);
-            gemv_res_norm(s, B, c.t_intermediate, x->dACT, TL(x, i, "mlp.down_proj.weight"), H, x->dH, x->ws,
-                          i + 1 < c.t_layers ? TL(x, i + 1, "input_layernorm.weight") : nullptr, eps, x->dHn,
-                          Lf ? Lf + gu_n + qkv_n + (size_t)H * NH * HD : nullptr);
+            gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, x->dSS, w.mf_gate_up);
+            gemv_res_norm(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws,
+                          i + 1 < c.t_layers ? x->w.t[i + 1].in_norm : nullptr, eps, x->dHn, w.mf_down);
             continue;
         }
-        gemv_geglu(s, B, x->dH, TL(x, i, "post_attention_layernorm.weight"), eps, TL(x, i, "mlp.gate_proj.weight"),
-                   c.t_intermediate, x->dACT);
-        gemv_res(s, B, c.t_intermediate, x->dACT, TL(x, i, "mlp.down_proj.weight"), H, x->dH, x->ws);
+        gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT);
+        gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws);
     }
     int nparts = 0;
     int64_t* nx = next_ids ? next_ids : x->d_next;
     // the step's last work also advances the device step state (pgmi_decode skips its host-side
     // set when the next call continues the sequence): lm_head's last workgroup, or argmax_finish
-    if (!gemv_logits(s, B, x->dH, W(x, "language_model.model.norm.weight"), eps, E, c.t_vocab, logits, x->pmax,
-                     x->pidx, &nparts, x->lm_done, nx, st, hist, adv_n))
+    if (!gemv_logits(s, B, x->dH, x->w.final_norm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts, x->lm_done, nx,
+                     st, hist, adv_n))
         argmax_finish(s, B, x->pmax, x->pidx, nparts, nx, st, hist, adv_n);
     return 0;
 }
@@ -1084,7 +1109,7 @@ int pgmi_prefill_probe(pgmi_ctx* x, int on) {
     if (!on && x->probe_on) x->prefill_graph = x->graph_before_probe;
     x->probe_on = on != 0;
     if (x->probe_on) x->prefill_graph = false;
-    clear_pgraphs(x);
+    x->pgraphs.clear();
     return 0;
 }
 
@@ -1107,7 +1132,7 @@ int pgmi_prefill_probe_times(pgmi_ctx* x, float* us, int n) {
 int pgmi_set_decode_staged_norm(pgmi_ctx* x, int on) {
     if (!x) return fail(PGMI_E_ARG, "null context");
     x->mf_staged = on < 0 ? -1 : on != 0;
-    clear_dgraphs(x);  // captured steps hold the other form's launches
+    x->dgraphs.clear();  // captured steps hold the other form's launches
     return 0;
 }
 
@@ -1115,7 +1140,7 @@ int pgmi_set_prefill_graph(pgmi_ctx* x, int on) {
     if (!x) return fail(PGMI_E_ARG, "null context");
     if (x->probe_on) x->graph_before_probe = on != 0;  // applied when the probe is turned off
     else x->prefill_graph = on != 0;
-    clear_pgraphs(x);
+    x->pgraphs.clear();
     return 0;
 }
 
@@ -1147,15 +1172,17 @@ static int ensure_mf_image(pgmi_ctx* x, hipStream_t s) {
         }
         x->allocs.push_back(p);
         x->mfw = reinterpret_cast<uint16_t*>(p);
-        clear_dgraphs(x);  // steps captured before held the row-major launches
+        x->dgraphs.clear();  // steps captured before held the row-major launches
     }
-    x->mfw_layer = per;
+    // the image's layout, defined here alone: [layer][gate|up 2 I x H | q|k|v QKVN x H | o_proj H x OK | down H x I]
     for (int i = 0; i < c.t_layers; ++i) {
-        uint16_t* L = x->mfw + per * i;
-        mf_swizzle(s, TL(x, i, "mlp.gate_proj.weight"), (int)(2 * I), (int)H, L);  // gate rows, then up rows
-        mf_swizzle(s, TL(x, i, "self_attn.q_proj.weight"), (int)QKVN, (int)H, L + 2 * I * H, true);  // q|k|v
-        mf_swizzle(s, TL(x, i, "self_attn.o_proj.weight"), (int)H, (int)OK, L + 2 * I * H + QKVN * H);
-        mf_swizzle(s, TL(x, i, "mlp.down_proj.weight"), (int)H, (int)I, L + 2 * I * H + QKVN * H + H * OK);
+        TextLayerW& w = x->w.t[i];
+        uint16_t *gu = x->mfw + per * i, *qkv = gu + 2 * I * H, *o = qkv + QKVN * H, *down = o + H * OK;
+        mf_swizzle(s, w.gate_up, (int)(2 * I), (int)H, gu);  // gate rows, then up rows
+        mf_swizzle(s, w.qkv, (int)QKVN, (int)H, qkv, true);  // q|k|v in the GEMV's row order
+        mf_swizzle(s, w.o, (int)H, (int)OK, o);
+        mf_swizzle(s, w.down, (int)H, (int)I, down);
+        w.mf_gate_up = gu; w.mf_qkv = qkv; w.mf_o = o; w.mf_down = down;
     }
     LAUNCHCHK();
     return 0;
@@ -1258,25 +1285,17 @@ static int decode_step(pgmi_ctx* x, const int64_t* ids, const void* embeds, int 
         gids = x->d_ids;
     }
     if (embeds) gids = nullptr;
-    GraphKey key{B, kv, kv_batch, kv_max, logits, next_ids, gids, embeds != nullptr, masked, n_steps, tokens, ragged};
-    GraphEntry& ge = x->graphs[key];
-    if (!ge.exec) {
-        if (ge.seen++ == 0) {  // first call with this key: run eagerly (sets kernel attributes)
-            if ((rc = body(s, gids, kv_max, false))) return rc;
-            LAUNCHCHK();
-            advanced();
-            return 0;
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        hipGraph_t g;
-        HIPCHK(hipStreamBeginCapture(x->cap_stream, hipStreamCaptureModeThreadLocal));
-        rc = body(x->cap_stream, gids, kv_max, false);
-        HIPCHK(hipStreamEndCapture(x->cap_stream, &g));
-        if (rc) return rc;
-        HIPCHK(hipGraphInstantiate(&ge.exec, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-    }
-    HIPCHK(hipGraphLaunch(ge.exec, s));
+    const std::vector<intptr_t> key{
+        B, (intptr_t)kv, kv_batch, kv_max, (intptr_t)logits, (intptr_t)next_ids,
+        (intptr_t)gids,      // the ids buffer the graph reads (the context's staging copy, or in place)
+        embeds != nullptr,   // the step's input is the staged embedding rows (pgmi_decode_embeds), not ids
+        masked,              // 0: no mask (a zero word), 1: staged bf16 mask (sum rounded), 2: staged fp32 mask
+        n_steps,             // decode steps captured back to back (pgmi_decode_steps; 1 otherwise)
+        (intptr_t)tokens,    // their per-step token record ([n_steps][B], may be null)
+        ragged};             // per-row step records (pgmi_decode_ragged): never aliases a lock-step graph
+    // eager under use_graph and captured alike: every launch sized for kv_max keys (the step record bounds them)
+    rc = run_graphed(x, x->dgraphs, s, key, [&](hipStream_t st) { return body(st, gids, kv_max, false); }, true);
+    if (rc) return rc;
     LAUNCHCHK();
     advanced();
     return 0;
@@ -1338,9 +1357,8 @@ int pgmi_lm_head(pgmi_ctx* x, const void* normed, int rows, float* logits, void*
     EpiArgs l{};
     l.out_f32 = logits;
     l.ldo = c.t_vocab;
-    gemm((hipStream_t)stream, reinterpret_cast<const uint16_t*>(normed), c.t_hidden,
-         W(x, "language_model.model.embed_tokens.weight"), c.t_hidden, rows, c.t_vocab, c.t_hidden, EPI_F32, l, x->ws,
-         x->ws_bytes);
+    gemm((hipStream_t)stream, reinterpret_cast<const uint16_t*>(normed), c.t_hidden, x->w.embed, c.t_hidden, rows,
+         c.t_vocab, c.t_hidden, EPI_F32, l, x->ws, x->ws_bytes);
     LAUNCHCHK();
     return 0;
 }
@@ -1450,17 +1468,15 @@ int pgmi_decode_kernel(pgmi_ctx* x, int which, int layer, int B, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const float eps = c.t_rms_eps;
     const int H = c.t_hidden;
+    const TextLayerW& w = x->w.t[layer];
     switch (which) {
-        case 1: gemv_res(s, B, c.t_heads * c.t_head_dim, x->dAO, TL(x, layer, "self_attn.o_proj.weight"), H, x->dH, x->ws); break;
-        case 2:
-            gemv_geglu(s, B, x->dH, TL(x, layer, "post_attention_layernorm.weight"), eps, TL(x, layer, "mlp.gate_proj.weight"),
-                       c.t_intermediate, x->dACT);
-            break;
-        case 3: gemv_res(s, B, c.t_intermediate, x->dACT, TL(x, layer, "mlp.down_proj.weight"), H, x->dH, x->ws); break;
+        case 1: gemv_res(s, B, c.t_heads * c.t_head_dim, x->dAO, w.o, H, x->dH, x->ws); break;
+        case 2: gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT); break;
+        case 3: gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws); break;
         case 4: {
             int nparts = 0;
-            gemv_logits(s, B, x->dH, W(x, "language_model.model.norm.weight"), eps,
-                        W(x, "language_model.model.embed_tokens.weight"), c.t_vocab, x->dlogits, x->pmax, x->pidx, &nparts);
+            gemv_logits(s, B, x->dH, x->w.final_norm, eps, x->w.embed, c.t_vocab, x->dlogits, x->pmax, x->pidx,
+                        &nparts);
             break;
         }
         default: return fail(PGMI_E_ARG, "unknown kernel id");
@@ -1489,19 +1505,20 @@ int pgmi_prefill_kernel(pgmi_ctx* x, int which, int layer, int rows, void* strea
     if (layer < 0 || layer >= c.t_layers) return fail(PGMI_E_ARG, "layer out of range");
     hipStream_t s = (hipStream_t)stream;
     const int H = c.t_hidden;
+    const TextLayerW& w = x->w.t[layer];
     switch (which) {
         case 0: {  // gate|up GEMM + GeGLU epilogue (modeling_gemma.py:134): Tn -> ACT
             EpiArgs g{};
             g.out = x->ACT; g.ldo = c.t_intermediate;
-            gemm(s, x->Tn, H, TL(x, layer, "mlp.gate_proj.weight"), H, rows, c.t_intermediate, H, EPI_GEGLU, g, x->ws,
-                 x->ws_bytes, c.t_intermediate);
+            gemm(s, x->Tn, H, w.gate_up, H, rows, c.t_intermediate, H, EPI_GEGLU, g, x->ws, x->ws_bytes,
+                 c.t_intermediate);
             break;
         }
         case 1: {  // down GEMM as the prefill runs it: split-K partials (reduced by the next norm)
             EpiArgs d{};
             d.res = x->Hs; d.ldr = H; d.out = x->Hs; d.ldo = H;
-            gemm(s, x->ACT, c.t_intermediate, TL(x, layer, "mlp.down_proj.weight"), c.t_intermediate, rows, H,
-                 c.t_intermediate, EPI_RES, d, x->ws, x->ws_bytes, 0, true);
+            gemm(s, x->ACT, c.t_intermediate, w.down, c.t_intermediate, rows, H, c.t_intermediate, EPI_RES, d, x->ws,
+                 x->ws_bytes, 0, true);
             break;
         }
         default: return fail(PGMI_E_ARG, "unknown kernel id");

@@ -80,7 +80,7 @@ class Engine:
             self.views[name.value.decode()] = self.slab[off.value: off.value + 2 * numel].view(torch.bfloat16).view(shp)
         self.prepared = False
         self._logits_buf = {}
-        self._ragged_buf = {}
+        self._gen_buf = {}  # generate(): per-batch-size step buffers
 
     def __del__(self):
         try:
@@ -485,68 +485,10 @@ class Engine:
         pgmi_decode_ragged) -- and generates what it would alone.  No mask, or all ones: the lock-step
         path.  kv defaults to new_kv(B, L + n_tokens + 1) either way."""
         ids = input_ids.to(self.device, torch.int64)
-        B, L = ids.shape
-        if attention_mask is not None and R.lengths_from_mask(attention_mask) is not None:
-            return self._generate_ragged(ids, attention_mask, pixel_values, n_tokens, graph, kv, do_sample,
-                                         temperature, top_p, generator, eos_token_id, pad_token_id, sync_every,
-                                         return_lengths)
-        if kv is None:
-            kv = self.new_kv(B, L + n_tokens + 1)
-        feats = self.project(self.vision(pixel_values))
-        logits = self.lm_forward(kv, 0, torch.arange(L).expand(B, L), ids=ids, image_feats=feats, logits_rows=2)
-        toks = torch.empty((B, n_tokens), dtype=torch.int64, device=self.device)
-        if do_sample:
-            us = torch.rand((n_tokens, B), device=self.device, generator=generator)
-            toks[:, 0] = self.sample_top_p(logits[:, 0], top_p, temperature, u=us[0])
-        else:
-            toks[:, 0] = self.argmax(logits[:, 0])
-        step_logits = torch.empty((B, self.cfgd["t_vocab"]), dtype=torch.float32, device=self.device)
-        nxt = torch.empty(B, dtype=torch.int64, device=self.device)
-        cur = toks[:, 0].clone()
-        stop = eos_token_id is not None
-        if stop:
-            pad = int(eos_token_id if pad_token_id is None else pad_token_id)
-            finished = torch.zeros(B, dtype=torch.int32, device=self.device)
-            alive = torch.empty(1, dtype=torch.int32, device=self.device)
-            self._eos_update(cur, finished, int(eos_token_id), pad, alive)
-            toks[:, 0] = cur
-        n_done = n_tokens
-        if not do_sample and not stop and graph and n_tokens > 1 and B >= self.GEN_MIN_BATCH:
-            # greedy without a stop token: GEN_CHUNK steps per hipGraph launch (pgmi_decode_steps), the
-            # argmax fed back in place and every step's token kept in a device record
-            rec = torch.empty((self.GEN_CHUNK, B), dtype=torch.int64, device=self.device)
-            t = 1
-            while t < n_tokens:
-                n = min(self.GEN_CHUNK, n_tokens - t)
-                self.decode_steps(cur, kv, L + t - 1, L + t, n, logits=step_logits, tokens=rec, graph=graph)
-                toks[:, t:t + n] = rec[:n].t()
-                t += n
-            return (toks, torch.full((B,), n_tokens, dtype=torch.int64, device=self.device)) if return_lengths else toks
-        for t in range(1, n_tokens):
-            if stop and (t - 1) % max(1, sync_every) == 0 and int(alive.item()) == 0:
-                n_done = t
-                break
-            if do_sample:
-                self.decode(cur, kv, L + t - 1, L + t, logits=step_logits, next_ids=nxt, graph=graph)
-                cur.copy_(self.sample_top_p(step_logits, top_p, temperature, u=us[t]))
-            else:  # greedy: the argmax is fed back in place (pgmi_decode with next_ids == ids)
-                self.decode(cur, kv, L + t - 1, L + t, logits=step_logits, next_ids=cur, graph=graph)
-            if stop:
-                self._eos_update(cur, finished, int(eos_token_id), pad, alive)
-            toks[:, t] = cur
-        if not stop:
-            return (toks, torch.full((B,), n_tokens, dtype=torch.int64, device=self.device)) if return_lengths else toks
-        toks = toks[:, :n_done]
-        hit = toks == int(eos_token_id)
-        first = torch.where(hit.any(1), hit.int().argmax(1) + 1, torch.full_like(hit[:, 0], n_done, dtype=torch.int64))
-        toks = toks[:, :int(first.max().item())].contiguous()
-        return (toks, first.to(torch.int64)) if return_lengths else toks
-
-    def _generate_ragged(self, ids, attention_mask, pixel_values, n_tokens, graph, kv, do_sample, temperature, top_p,
-                         generator, eos_token_id, pad_token_id, sync_every, return_lengths):
-        """generate() for a padded batch: the same three loops on the per-row step (decode_ragged)."""
-        ids, lens = R.right_pad(ids, attention_mask)
-        ids = ids.contiguous()
+        lens = R.lengths_from_mask(attention_mask) if attention_mask is not None else None
+        if lens is not None:
+            ids, lens = R.right_pad(ids, attention_mask)
+            ids = ids.contiguous()
         B, L = ids.shape
         if kv is None:
             kv = self.new_kv(B, L + n_tokens + 1)
@@ -559,18 +501,31 @@ class Engine:
             toks[:, 0] = self.sample_top_p(logits[:, 0], top_p, temperature, u=us[0])
         else:
             toks[:, 0] = self.argmax(logits[:, 0])
-        # per-B persistent buffers (step logits, fed-back ids, chunk record): stable pointers, so repeated
-        # generate calls on the same cache replay the decode graphs they captured
-        bufs = self._ragged_buf.get(B)
+        # per-B persistent buffers (step logits, fed-back ids, sampled step's argmax, chunk record): stable
+        # pointers, so repeated generate calls on the same cache replay the decode graphs they captured
+        bufs = self._gen_buf.get(B)
         if bufs is None:
             bufs = (torch.empty((B, self.cfgd["t_vocab"]), dtype=torch.float32, device=self.device),
                     torch.empty(B, dtype=torch.int64, device=self.device),
                     torch.empty(B, dtype=torch.int64, device=self.device),
                     torch.empty((self.GEN_CHUNK, B), dtype=torch.int64, device=self.device))
-            self._ragged_buf[B] = bufs
+            self._gen_buf[B] = bufs
         step_logits, cur, nxt, rec = bufs
         cur.copy_(toks[:, 0])
-        lens = lens.to(torch.int32)
+        # step(t, next_ids) / step(t, None, n, rec): the decode step(s) producing token t (.. t + n - 1) from `cur`
+        # -- all the two forms differ in after the prefill (lock-step: one KV row and position; ragged: a row's own)
+        if lens is None:
+            def step(t, next_ids, n=1, tokens=None):
+                if tokens is not None:  # pgmi_decode_steps: the argmax is fed back in place
+                    self.decode_steps(cur, kv, L + t - 1, L + t, n, logits=step_logits, tokens=tokens, graph=graph)
+                else:
+                    self.decode(cur, kv, L + t - 1, L + t, logits=step_logits, next_ids=next_ids, graph=graph)
+        else:
+            lens = lens.to(torch.int32)
+
+            def step(t, next_ids, n=1, tokens=None):
+                self.decode_ragged(cur, kv, lens + (t - 1), lens + t, n, logits=step_logits, tokens=tokens,
+                                   next_ids=next_ids, graph=graph)
         stop = eos_token_id is not None
         if stop:
             pad = int(eos_token_id if pad_token_id is None else pad_token_id)
@@ -579,29 +534,30 @@ class Engine:
             self._eos_update(cur, finished, int(eos_token_id), pad, alive)
             toks[:, 0] = cur
         n_done = n_tokens
-        full = torch.full((B,), n_tokens, dtype=torch.int64, device=self.device)
         if not do_sample and not stop and graph and n_tokens > 1 and B >= self.GEN_MIN_BATCH:
+            # greedy without a stop token: GEN_CHUNK steps per hipGraph launch (pgmi_decode_steps / _ragged), the
+            # argmax fed back in place and every step's token kept in a device record
             t = 1
             while t < n_tokens:
                 n = min(self.GEN_CHUNK, n_tokens - t)
-                self.decode_ragged(cur, kv, lens + (t - 1), lens + t, n, logits=step_logits, tokens=rec, graph=graph)
+                step(t, None, n, rec)
                 toks[:, t:t + n] = rec[:n].t()
                 t += n
-            return (toks, full) if return_lengths else toks
-        for t in range(1, n_tokens):
-            if stop and (t - 1) % max(1, sync_every) == 0 and int(alive.item()) == 0:
-                n_done = t
-                break
-            if do_sample:
-                self.decode_ragged(cur, kv, lens + (t - 1), lens + t, logits=step_logits, next_ids=nxt, graph=graph)
-                cur.copy_(self.sample_top_p(step_logits, top_p, temperature, u=us[t]))
-            else:  # greedy: the argmax is fed back in place
-                self.decode_ragged(cur, kv, lens + (t - 1), lens + t, logits=step_logits, next_ids=cur, graph=graph)
-            if stop:
-                self._eos_update(cur, finished, int(eos_token_id), pad, alive)
-            toks[:, t] = cur
+        else:
+            for t in range(1, n_tokens):
+                if stop and (t - 1) % max(1, sync_every) == 0 and int(alive.item()) == 0:
+                    n_done = t
+                    break
+                if do_sample:
+                    step(t, nxt)
+                    cur.copy_(self.sample_top_p(step_logits, top_p, temperature, u=us[t]))
+                else:  # greedy: the argmax is fed back in place (next_ids == ids)
+                    step(t, cur)
+                if stop:
+                    self._eos_update(cur, finished, int(eos_token_id), pad, alive)
+                toks[:, t] = cur
         if not stop:
-            return (toks, full) if return_lengths else toks
+            return (toks, torch.full((B,), n_tokens, dtype=torch.int64, device=self.device)) if return_lengths else toks
         toks = toks[:, :n_done]
         hit = toks == int(eos_token_id)
         first = torch.where(hit.any(1), hit.int().argmax(1) + 1, torch.full_like(hit[:, 0], n_done, dtype=torch.int64))

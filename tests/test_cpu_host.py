@@ -83,6 +83,9 @@ def test_create_validates_config_without_gpu():
     assert total == 2_923_466_480  # SURVEY.md sec.3.5 (the tied lm_head counted once)
     assert lib.pgmi_weights_bytes(h) >= 2 * total
     assert lib.pgmi_kv_bytes(h, 1, 1024) == 18 * 2 * 1024 * 256 * 2
+    # graph caches (0 prefill, 1 decode): empty on a fresh, unprepared context; -1 without a context
+    assert lib.pgmi_graph_count(h, 0) == 0 and lib.pgmi_graph_count(h, 1) == 0
+    assert lib.pgmi_graph_count(None, 0) == -1 and lib.pgmi_graph_count(None, 1) == -1
     lib.pgmi_destroy(h)
     # invalid configs are rejected with PGMI_E_ARG and a message
     c.t_kv_heads = 2

@@ -509,3 +509,109 @@ def test_prefill_probe_kernel_events(eng, gold):
     assert all(1.0 < v < 5000.0 for v in t), t
     again = eng.lm_forward(kv, 0, pos, ids=ids, image_feats=feats, logits_rows=1)
     assert torch.equal(again, ref)
+
+
+# ---------------------------------------------------------------- the two graph caches (pgmi_graph_count)
+GRAPH_CACHE_MAX = 64  # include/pgmi.h PGMI_GRAPH_CACHE_MAX
+
+
+def graph_count(eng, which):
+    """Keys in the context's prefill (0) or decode (1) graph cache."""
+    return eng.lib.pgmi_graph_count(eng.ctx, which)
+
+
+def _prefilled(eng, gold, B, kv):
+    """Prefill kv with B copies of the golden prompt (flipped images); returns (L, first tokens)."""
+    px = torch.from_numpy(O.from_bits(gold["pixels_bits"])).cuda()
+    pxs = torch.stack([px[0], px[0].flip(-1), px[0].flip(-2), px[0].flip(-1).flip(-2)])[:B].contiguous()
+    ids = torch.from_numpy(gold["ids"]).cuda().expand(B, -1).contiguous()
+    L = ids.shape[1]
+    lg = eng.lm_forward(kv, 0, torch.arange(L).expand(B, L), ids=ids, image_feats=eng.project(eng.vision(pxs)),
+                        logits_rows=1)
+    return L, eng.argmax(lg[:, 0]), ids, pxs
+
+
+def test_decode_graph_cache_is_bounded(eng, gold):
+    """The decode graph cache holds at most PGMI_GRAPH_CACHE_MAX keys: 70 distinct logits buffers (70 keys, each
+    called twice: eager, then capture + launch) never leave more than 64 entries behind, and a step run through
+    a cache that was dropped on the way still returns the eager step's logits bit for bit."""
+    eng.set_decode_staged_norm(-1)  # an empty decode cache to start from
+    assert graph_count(eng, 1) == 0
+    kv = eng.new_kv(1, 512)
+    L, cur, _, _ = _prefilled(eng, gold, 1, kv)
+    V = eng.cfgd["t_vocab"]
+    bufs = [torch.empty((1, V), dtype=torch.float32, device="cuda") for _ in range(70)]  # all alive: 70 addresses
+    assert len({b.data_ptr() for b in bufs}) == 70
+    counts = []
+    for b in bufs:
+        for _ in range(2):
+            eng.decode(cur, kv, L, L + 1, logits=b, graph=True)
+            counts.append(graph_count(eng, 1))
+    torch.cuda.synchronize()
+    assert max(counts) <= GRAPH_CACHE_MAX, counts
+    assert max(counts) == GRAPH_CACHE_MAX and counts[-1] < GRAPH_CACHE_MAX, counts  # filled, then dropped
+    want = eng.decode(cur, kv, L, L + 1, graph=False)
+    torch.cuda.synchronize()
+    assert torch.equal(bufs[-1], want)
+    assert torch.equal(bufs[0], want)
+
+
+@pytest.mark.parametrize("B,n_tokens", [(4, 10), (1, 6)])
+def test_repeated_generate_replays_its_graphs(eng, gold, B, n_tokens):
+    """Lock-step generate keeps its step buffers per batch size, so calls on the same cache replay the decode
+    graphs they captured instead of capturing new ones: B = 4 runs two chunks of the multi-step path (8 steps,
+    then 1), B = 1 the single-step path.  Every call returns the eager loop's tokens."""
+    px = torch.from_numpy(O.from_bits(gold["pixels_bits"])).cuda()
+    pxs = torch.stack([px[0], px[0].flip(-1), px[0].flip(-2), px[0].flip(-1).flip(-2)])[:B].contiguous()
+    ids = torch.from_numpy(gold["ids"]).cuda().expand(B, -1).contiguous()
+    kv = eng.new_kv(B, ids.shape[1] + n_tokens + 1)
+    want = eng.generate(ids, pxs, n_tokens, graph=False, kv=kv)
+    got, counts = [], []
+    for _ in range(3):
+        got.append(eng.generate(ids, pxs, n_tokens, graph=True, kv=kv))
+        counts.append(graph_count(eng, 1))
+    torch.cuda.synchronize()
+    assert counts[2] == counts[1], counts
+    for i, g in enumerate(got):
+        assert torch.equal(g, want), (i, g, want)
+
+
+def test_graph_caches_clear_selectively(eng, gold):
+    """pgmi_set_prefill_graph drops the prefill graphs only, pgmi_set_decode_staged_norm the decode graphs only,
+    pgmi_prepare both."""
+    from pgmi import _native as N
+    c = eng.cfgd
+    n_img = (c["v_image"] // c["v_patch"]) ** 2
+    kv = eng.new_kv(1, 512)
+    L, cur, ids, pxs = _prefilled(eng, gold, 1, kv)
+    pos = torch.arange(L)[None].contiguous()
+    feats = eng.project(eng.vision(pxs))
+    # fixed buffers: the prefill key is every pointer the call reads or writes
+    logits = torch.empty((1, 1, c["t_vocab"]), dtype=torch.float32, device="cuda")
+    step_logits = eng.logits_buffer(1)
+
+    def prefill_pair():
+        for _ in range(2):
+            N.check(eng.lib.pgmi_lm_forward(eng.ctx, ids.data_ptr(), feats.data_ptr(), n_img, None, 1, L,
+                                            pos.data_ptr(), kv.data_ptr(), 1, kv.shape[3], 0, logits.data_ptr(), 1,
+                                            eng._s()))
+
+    def decode_pair():
+        for _ in range(2):
+            eng.decode(cur, kv, L, L + 1, logits=step_logits, graph=True)
+
+    prefill_pair()
+    decode_pair()
+    n0, n1 = graph_count(eng, 0), graph_count(eng, 1)
+    assert n0 > 0 and n1 > 0
+    eng.set_prefill_graph(True)
+    assert (graph_count(eng, 0), graph_count(eng, 1)) == (0, n1)
+    prefill_pair()
+    n0 = graph_count(eng, 0)
+    assert n0 > 0
+    eng.set_decode_staged_norm(-1)
+    assert (graph_count(eng, 0), graph_count(eng, 1)) == (n0, 0)
+    decode_pair()
+    assert graph_count(eng, 1) > 0
+    eng.prepare()
+    assert (graph_count(eng, 0), graph_count(eng, 1)) == (0, 0)
