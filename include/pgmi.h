@@ -267,7 +267,8 @@ int pgmi_prefill_kernel(pgmi_ctx* ctx, int which, int layer, int rows, void* str
 int pgmi_prefill_probe(pgmi_ctx* ctx, int on);
 int pgmi_prefill_probe_times(pgmi_ctx* ctx, float* us, int n);
 /* Tuning hook: force the prefill GEMM tile configuration and split-K factor for subsequent
- * calls (kernels_gemm.hip enum Cfg: 0-5 register-staged tiles, 6-29 LDS-DMA panel tiles, 30-35 warp-specialised panel tiles);
+ * calls (kernels_gemm.hip PGMI_GEMM_CFGS: 11-28 LDS-DMA panel tiles, 30-34 and 38 warp-specialised panel tiles,
+ * 36-37 8-phase tiles; an id not in that list is PGMI_E_ARG); a dual (GeGLU) GEMM never splits;
  * cfg < 0 restores the automatic (measured) plan. */
 int pgmi_tune_gemm(int cfg, int split);
 /* Tuning hook: the same for ONE GEMM shape (M x N x K, dual = the gate|up GeGLU form) while every
@@ -281,6 +282,10 @@ int pgmi_tune_gemm_shape(int M, int N, int K, int dual, int cfg, int split);
  * block raster of kernels_gemm.hip xcd_tile); mt/nt/z receive n_mt*n_nt*S entries indexed by the linear
  * workgroup id.  Returns the XCD block code the launch uses (0 = run order); no device needed. */
 int pgmi_debug_gemm_tiles(int n_mt, int n_nt, int S, int BM, int BN, int K, int* mt, int* nt, int* z);
+/* Test hook: the plan a prefill GEMM of M x N x K (dual = the gate|up GeGLU form) gets -- tile configuration id,
+ * tile rows bm and columns bn (dual: per operand), split-K factor -- under the tuning overrides in force; a
+ * launch may still lower the split (workspace size, N % 4, empty K ranges).  No device needed. */
+int pgmi_debug_gemm_plan(int M, int N, int K, int dual, int* cfg, int* bm, int* bn, int* split);
 
 /* Tuning hook: force the prefill attention kernel (kernels_attn.hip): 0 = 16-row kernel with
  * LDS-resident scores, 7 = one pass with K/V loaded once and scores in registers (head_dim 72, <= 256 keys),

@@ -1532,14 +1532,20 @@ int pgmi_debug_gemm_tiles(int n_mt, int n_nt, int S, int BM, int BN, int K, int*
     return gemm_tile_order(n_mt, n_nt, S, BM, BN, K, mt, nt, z);
 }
 
+int pgmi_debug_gemm_plan(int M, int N, int K, int dual, int* cfg, int* bm, int* bn, int* split) {
+    if (M < 1 || N < 1 || K < 1 || !cfg || !bm || !bn || !split) return fail(PGMI_E_ARG, "bad argument");
+    gemm_plan(M, N, K, dual, cfg, bm, bn, split);
+    return 0;
+}
+
 int pgmi_tune_gemm(int cfg, int split) {
-    if (cfg >= kGemmCfgs || split < 0 || split > 32) return fail(PGMI_E_ARG, "bad GEMM plan");
+    if ((cfg >= 0 && !gemm_cfg_valid(cfg)) || split < 0 || split > 32) return fail(PGMI_E_ARG, "bad GEMM plan");
     gemm_force_plan(cfg, split);
     return 0;
 }
 
 int pgmi_tune_gemm_shape(int M, int N, int K, int dual, int cfg, int split) {
-    if (cfg >= kGemmCfgs || split < 0 || split > 16) return fail(PGMI_E_ARG, "bad GEMM plan");
+    if ((cfg >= 0 && !gemm_cfg_valid(cfg)) || split < 0 || split > 16) return fail(PGMI_E_ARG, "bad GEMM plan");
     if (gemm_force_shape(M, N, K, dual, cfg, split)) return fail(PGMI_E_ARG, "too many per-shape GEMM plans");
     return 0;
 }

@@ -5,12 +5,10 @@
 // prefill (modeling_siglip.py:45-51,92-95,154-155; modeling_gemma.py:129-131,220-223,
 // 391,433) with the reference's rounding points fused into the epilogue.
 //
-// Tile: BM x BN x 64 over a grid of waves (below); A/B tiles staged global -> registers ->
-// LDS (double buffered, one barrier per k-tile, next tile's global loads in flight during
-// the MFMAs).  LDS rows
-// are padded to 72 bf16 (144 B) so the 16 rows a ds_read_b128 lane group touches land
-// on distinct banks.  Split-K (grid.z) writes fp32 partial slabs that a separate
-// epilogue kernel reduces in a fixed order (bitwise reproducible).
+// Tile: BM x BN x 64 over a grid of waves; A/B tiles go global -> LDS by LDS-DMA (the panel,
+// warp-specialised and 8-phase kernels below).  Split-K (the grid's second dimension) writes fp32
+// partial slabs that a separate epilogue kernel, or the consumer kernel, reduces in a fixed order
+// (bitwise reproducible).
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -27,7 +25,6 @@
 namespace pgmi {
 
 constexpr int BK = 64;
-constexpr int LDSK = 72;  // padded row (elements)
 
 // Probe builds only (tools/build_variant.sh "-DPGMI_GEMM_DIAG=n"; never set in the product build): bit 0 = the
 // panel kernels' compute waves read their fragments but issue no MFMA, bit 1 = the LDS-DMA stages issue no
@@ -243,139 +240,6 @@ __device__ __forceinline__ void rope_apply(const EpiArgs& ea, int M, int mb, int
                     ea.vc + b * ea.kv_b_stride + (long)(ea.kv_start + l) * (ea.nkv * 256) + (h - ea.nh - ea.nkv) * 256;
                 dst[d] = f2bf(x0);
                 dst[d + 128] = f2bf(x1);
-            }
-        }
-}
-
-// SPLIT: write raw fp32 partials to ws[z][M][N] (z = blockIdx.z) instead of the epilogue.
-// Wave grid WGM x WGN; each wave owns TM x TN 16x16 MFMA tiles, so BM = WGM*TM*16 and
-// BN = WGN*TN*16.  Small-M prefill GEMMs (M = 256 vision rows, 288 text rows) use one
-// workgroup per BN columns covering ALL rows (WGM = 4 or 6, WGN = 1): every weight byte is
-// read from HBM once, the activation panel is re-read from L2.
-template <int WGM, int WGN, int TM, int TN, int EPI, bool SPLIT>
-__global__ void __launch_bounds__(64 * WGM * WGN) k_gemm(const uint16_t* __restrict__ A, int lda,
-                                                         const uint16_t* __restrict__ W, int ldw, int M, int N, int K,
-                                                         int kt_per_split, EpiArgs ea, float* __restrict__ ws,
-                                                         long up_off) {
-    constexpr bool DUAL = (EPI == EPI_GEGLU);
-    constexpr int NT = 64 * WGM * WGN;
-    constexpr int BM = WGM * TM * 16, BN = WGN * TN * 16;
-    constexpr int ACH = (BM * 8 + NT - 1) / NT;  // 16-B chunks of the A tile per thread
-    constexpr int BCH = (BN * 8 + NT - 1) / NT;
-    constexpr int NB = DUAL ? 2 : 1;
-    extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
-    uint16_t* As = smem;                         // [2][BM][LDSK]
-    uint16_t* Bs = smem + 2 * BM * LDSK;         // [2][NB][BN][LDSK]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave / WGN, wc = wave % WGN;
-    const int n0 = blockIdx.x * BN, m0 = blockIdx.y * BM;
-    const int nkt_total = (K + BK - 1) / BK;
-    const int kt0 = blockIdx.z * kt_per_split;
-    int kt1 = kt0 + kt_per_split;
-    if (kt1 > nkt_total) kt1 = nkt_total;
-    const int nkt = kt1 - kt0;
-
-    f32x4 acc[NB][TM][TN];
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // two register stages (named, statically indexed) + two LDS buffers: the global loads of
-    // k-tile t+2 are in flight while tile t is multiplied and tile t+1 is written to LDS
-    uint4 ra0[ACH], rb0[NB][BCH], ra1[ACH], rb1[NB][BCH];
-    auto gload = [&](int kt, uint4 (&ra)[ACH], uint4 (&rb)[NB][BCH]) {
-        const int kbase = kt * BK;
-#pragma unroll
-        for (int i = 0; i < ACH; ++i) {
-            const int c = tid + NT * i, r = c >> 3, kc = (c & 7) * 8;
-            const int gm = m0 + r, gk = kbase + kc;
-            ra[i] = (c < BM * 8 && gm < M && gk < K) ? ldg16(A + (long)gm * lda + gk) : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int i = 0; i < BCH; ++i) {
-                const int c = tid + NT * i, r = c >> 3, kc = (c & 7) * 8;
-                const int gn = n0 + r, gk = kbase + kc;
-                rb[b][i] = (c < BN * 8 && gn < N && gk < K) ? ldg16(W + b * up_off + (long)gn * ldw + gk)
-                                                             : make_uint4(0, 0, 0, 0);
-            }
-    };
-    auto lstore = [&](int buf, const uint4 (&ra)[ACH], const uint4 (&rb)[NB][BCH]) {
-#pragma unroll
-        for (int i = 0; i < ACH; ++i) {
-            const int c = tid + NT * i, r = c >> 3, kc = (c & 7) * 8;
-            if (c < BM * 8) *reinterpret_cast<uint4*>(As + (buf * BM + r) * LDSK + kc) = ra[i];
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-#pragma unroll
-            for (int i = 0; i < BCH; ++i) {
-                const int c = tid + NT * i, r = c >> 3, kc = (c & 7) * 8;
-                if (c < BN * 8) *reinterpret_cast<uint4*>(Bs + ((buf * NB + b) * BN + r) * LDSK + kc) = rb[b][i];
-            }
-    };
-    auto compute = [&](int buf) {
-#pragma unroll
-        for (int kk = 0; kk < BK / 32; ++kk) {
-            const int kof = kk * 32 + 8 * (lane >> 4);
-            short8 af[TM], bfr[NB][TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-                af[i] = *reinterpret_cast<const short8*>(As + (buf * BM + (wr * TM + i) * 16 + (lane & 15)) * LDSK + kof);
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    bfr[b][j] = *reinterpret_cast<const short8*>(
-                        Bs + ((buf * NB + b) * BN + (wc * TN + j) * 16 + (lane & 15)) * LDSK + kof);
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[b][i][j] = mfma16(af[i], bfr[b][j], acc[b][i][j]);
-        }
-    };
-
-    if (nkt > 0) gload(kt0, ra0, rb0);
-    if (nkt > 1) gload(kt0 + 1, ra1, rb1);
-    if (nkt > 0) lstore(0, ra0, rb0);
-    __syncthreads();
-    // iteration t: issue loads of t+2 into the register set that held t, multiply buffer t&1,
-    // write tile t+1 (loaded one iteration earlier) into the other buffer, barrier
-    for (int t = 0; t < nkt; t += 2) {
-        if (t + 2 < nkt) gload(kt0 + t + 2, ra0, rb0);
-        compute(0);
-        if (t + 1 < nkt) lstore(1, ra1, rb1);
-        __syncthreads();
-        if (t + 1 >= nkt) break;
-        if (t + 3 < nkt) gload(kt0 + t + 3, ra1, rb1);
-        compute(1);
-        if (t + 2 < nkt) lstore(0, ra0, rb0);
-        __syncthreads();
-    }
-
-    // C/D map of 16x16x32: col = lane & 15, row = (lane >> 4) * 4 + r
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wc * TN + j) * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + (wr * TM + i) * 16 + (lane >> 4) * 4 + r;
-                if (m < M && n < N) {
-                    if constexpr (SPLIT) {
-                        ws[((long)blockIdx.z * M + m) * N + n] = acc[0][i][j][r];
-                    } else {
-                        epi_store<EPI>(ea, m, n, acc[0][i][j][r], DUAL ? acc[NB - 1][i][j][r] : 0.f);
-                    }
-                }
             }
         }
 }
@@ -622,6 +486,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_gemm_p(const uint16_t* __restric
         PGMI_SB();
         slot = nslot;
     }
+#undef PGMI_LDS_AT
 #undef PGMI_READ_FRAGS
 #undef PGMI_MFMAS
 #undef PGMI_SB
@@ -712,7 +577,7 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_gemm_w(const uint16_t* __
             src[i] = base + (long)row * ld + gk[i];
         }
         const uint16_t* zero = reinterpret_cast<const uint16_t*>(g_zero_chunk);
-        // one row tile (n_mt == 1, flagged in bit 30 of code by launch_w): every weight byte is read by one
+        // one row tile (n_mt == 1, flagged in bit 30 of code by the launcher): every weight byte is read by one
         // workgroup once, so those pieces stream non-temporal; the activation panel, which every workgroup
         // re-reads, keeps the default policy.  Same box (tools/archive/gpu_r4l.sh, the M = 288 gate|up): 43.1 / 43.8 /
         // 43.3 -> 41.2 / 41.7 / 41.4 us in situ, 224 px prefill 3.80 -> 3.77-3.79 ms
@@ -1208,56 +1073,88 @@ __global__ void __launch_bounds__(512, 1) k_gemm_8p(const uint16_t* __restrict__
 
 // (PGMI_GEMM_KERNELS_ONLY: the kernel templates alone, for single-instantiation ISA / register checks)
 #ifndef PGMI_GEMM_KERNELS_ONLY
-// Tile configurations (wave grid, per-wave MFMA tiles).  BM = WGM*TM*16, BN = WGN*TN*16.
+// Tile configurations.  Each is defined once, on its line here; the enum, BM / BN, the launch, the deferred
+// partials and the RoPE form are all derived from it (Tile, with_cfg).
+//   X(id, name, family, NW, WM, TM, TNW, ST, LW, RL, ROPE)
+// family FAM_P = k_gemm_p, FAM_W = k_gemm_w (NW compute waves + LW loader waves; RL = its in-wave reload mode),
+// FAM_8 = k_gemm_8p (two K-tile buffers).  NW waves in a WM x NW/WM grid, each TM x TNW 16x16 MFMA tiles (TNW
+// per B operand for plain GEMMs; the dual gate|up GEMM splits them over gate and up), ST ring slots:
+// BM = WM*TM*16, BN = (NW/WM)*TNW*16 (dual: BN/2 gate + BN/2 up columns).  ROPE: the configuration has a
+// RoPE-epilogue form (two 16-column tiles per wave and a tile width dividing 256) -- stated, not derived:
+// Q256w has the tiles and no RoPE form on purpose (see its row in choose()'s table).
+// The ids are cited by tools, DESIGN.md and profiles/ and stay as they are; the gaps are retired candidates
+// (DESIGN.md lists them: restoring one for a sweep is one line here).
+enum Fam { FAM_P, FAM_W, FAM_8 };
+#define PGMI_GEMM_CFGS(X)                                                                                      \
+    /* panel GEMM (k_gemm_p, LDS-DMA ring) */                                                                  \
+    X(11, P128w, FAM_P, 4, 2, 4, 4, 3, 0, false, false)    /* 128 x 128 */                                     \
+    X(14, P64x64, FAM_P, 4, 2, 2, 2, 6, 0, false, true)    /* small GEMMs: every CU busy, little A per CU */   \
+    X(16, P64x128, FAM_P, 4, 2, 2, 4, 6, 0, false, false)                                                      \
+    /* 8 waves (2 per SIMD: one wave's LDS-DMA issue stalls overlap its partner's MFMAs) */                    \
+    X(22, Q256w, FAM_P, 8, 2, 8, 2, 3, 0, false, false)    /* 256 x 128 */                                     \
+    /* shallow rings (2-3 workgroups per CU: more k-tiles in flight per CU for the small GEMMs) */             \
+    X(25, P64x64s4, FAM_P, 4, 2, 2, 2, 4, 0, false, true)                                                      \
+    X(26, P32x64s4, FAM_P, 4, 2, 1, 2, 4, 0, false, true)                                                      \
+    X(27, P64x32s4, FAM_P, 4, 2, 2, 1, 4, 0, false, false)                                                     \
+    X(28, P96x64s4, FAM_P, 4, 2, 3, 2, 4, 0, false, true)  /* M = 288 = 3 x 96 */                              \
+    /* warp-specialised (k_gemm_w): compute waves + 4 LDS-DMA loader waves */                                  \
+    X(30, W288w, FAM_W, 8, 2, 9, 2, 3, 4, false, true)     /* 288 x 128 */                                     \
+    X(31, W288n, FAM_W, 8, 2, 9, 1, 3, 4, false, false)    /* 288 x 64 */                                      \
+    X(32, W64x64, FAM_W, 4, 2, 2, 2, 6, 4, false, true)                                                        \
+    X(33, W352w, FAM_W, 8, 2, 11, 2, 2, 4, false, true)    /* 352 x 128 (448 px text rows: 1056 = 3 x 352) */  \
+    X(34, W128x128, FAM_W, 8, 2, 4, 2, 4, 4, false, true)                                                      \
+    /* 8-phase (k_gemm_8p): BN 256 (dual: 128 gate + 128 up) */                                                \
+    X(36, E256, FAM_8, 8, 2, 8, 4, 2, 0, false, false)     /* 256 rows */                                      \
+    X(37, E192, FAM_8, 8, 2, 6, 4, 2, 0, false, false)     /* 192 rows */                                      \
+    /* round 6: k_gemm_w's in-wave reload mode (W288w's tiles; bit-identical results) */                       \
+    X(38, R288w, FAM_W, 8, 2, 9, 2, 3, 4, true, false)
+
 enum Cfg : int {
-    C288x64 = 0,   // 6x1 waves, 3x4 tiles  (text rows: M = 288 = 18 x 16)
-    C288x32 = 1,   // 6x1 waves, 3x2 tiles
-    C256x64 = 2,   // 4x1 waves, 4x4 tiles  (vision rows: M = 256)
-    C256x32 = 3,   // 4x1 waves, 4x2 tiles
-    C128x128 = 4,  // 2x2 waves, 4x4 tiles  (large M)
-    C128x64 = 5,   // 2x2 waves, 4x2 tiles
-    // panel GEMM (k_gemm_p, LDS-DMA ring): BM x BN output columns (dual gate/up: BN/2 columns x 2)
-    P288w = 6,     // TM 9,  BN 128, 3 slots
-    P256w = 7,     // TM 8,  BN 128, 3 slots
-    P352w = 8,     // TM 11, BN 128, 2 slots  (448 px text rows: M = 1056 = 3 x 352)
-    P288n = 9,     // TM 9,  BN 64,  3 slots
-    P256n = 10,    // TM 8,  BN 64,  3 slots
-    P128w = 11,    // TM 4,  BN 128, 3 slots
-    P288t = 12,    // TM 9,  BN 32,  4 slots  (2x2 waves, 1 column fragment each)
-    P256t = 13,    // 4x1 waves, TM 4, BN 32, 4 slots
-    P64x64 = 14,   // TM 2, BN 64,  6 slots   (small GEMMs: every CU busy, little A per CU)
-    P128x64 = 15,  // TM 4, BN 64,  6 slots
-    P64x128 = 16,  // TM 2, BN 128, 6 slots
-    P128x128 = 17, // TM 4, BN 128, 5 slots
-    P64x64d = 18,  // TM 2, BN 64,  10 slots
-    P128x64d = 19, // 4x1 waves, TM 2, BN 64, 6 slots
-    // 8 waves (2 per SIMD: one wave's LDS-DMA issue stalls overlap its partner's MFMAs)
-    Q288w = 20,    // 2x4 waves, TM 9,  BN 128, 3 slots
-    Q352w = 21,    // 2x4 waves, TM 11, BN 128, 2 slots
-    Q256w = 22,    // 2x4 waves, TM 8,  BN 128, 3 slots
-    Q288x256 = 23, // 2x4 waves, TM 9,  BN 256, 2 slots
-    // shallow rings (2-3 workgroups per CU: more k-tiles in flight per CU for the small GEMMs)
-    P64x64s3 = 24, // TM 2, BN 64, 3 slots
-    P64x64s4 = 25, // TM 2, BN 64, 4 slots
-    P32x64s4 = 26, // TM 1, BN 64, 4 slots
-    P64x32s4 = 27, // TM 2, BN 32, 4 slots
-    P96x64s4 = 28, // TM 3, BN 64, 4 slots (M = 288 = 3 x 96)
-    P96x64s3 = 29, // TM 3, BN 64, 3 slots
-    // warp-specialised (k_gemm_w): compute waves + 4 LDS-DMA loader waves
-    W288w = 30,    // 2x4 compute waves, TM 9,  BN 128, 3 slots
-    W288n = 31,    // 2x4 compute waves, TM 9,  BN 64,  3 slots
-    W64x64 = 32,   // 2x2 compute waves, TM 2,  BN 64,  6 slots
-    W352w = 33,    // 2x4 compute waves, TM 11, BN 128, 2 slots
-    W128x128 = 34, // 2x4 compute waves, TM 4,  BN 128, 4 slots
-    W128x64 = 35,  // 2x2 compute waves, TM 4,  BN 64,  5 slots
-    // 8-phase (k_gemm_8p): 2x4 waves, BN 256 (dual: 128 gate + 128 up), two K-tile buffers
-    E256 = 36,     // TM 8: 256 rows
-    E192 = 37,     // TM 6: 192 rows
-    // round 6: k_gemm_w's in-wave reload mode (W288w's tiles; bit-identical results)
-    R288w = 38,    // 2x4 compute waves, TM 9, BN 128 (dual 64 + 64), 3 slots
-    kNumCfg = 39,
+#define X(id, name, ...) name = id,
+    PGMI_GEMM_CFGS(X)
+#undef X
 };
-static_assert(kNumCfg == kGemmCfgs, "launch.h kGemmCfgs");
+
+template <Fam F, int NW, int WM, int TM, int TNW, int ST, int LW, bool RL, bool ROPE_>
+struct Tile {
+    static constexpr Fam FAM = F;
+    static constexpr bool ROPE = ROPE_;
+    static constexpr int BM = WM * TM * 16;
+    static constexpr int THREADS = 64 * (NW + LW);
+    // what depends on the epilogue: the dual GEMM keeps the B rows per slot
+    template <int EPI>
+    struct For {
+        static constexpr int NB = EPI == EPI_GEGLU ? 2 : 1;
+        static constexpr int TN = NB == 2 ? (TNW >= 2 ? TNW / 2 : 1) : TNW;
+        static constexpr int BN = (NW / WM) * TN * 16;
+        static constexpr size_t SLOT = (size_t)(BM + NB * BN) * 128;
+        static constexpr int STQ = (F != FAM_P || ST * SLOT <= 163840) ? ST : ST - 1;  // k_gemm_p: fit 160 KiB
+        static constexpr size_t LDS = STQ * SLOT;
+        static_assert(LDS <= 163840, "LDS ring exceeds 160 KiB");
+        template <bool SPLIT>
+        static constexpr auto kernel() {
+            if constexpr (F == FAM_P) return &k_gemm_p<NW, WM, TM, TN, NB, STQ, EPI, SPLIT>;
+            else if constexpr (F == FAM_W) return &k_gemm_w<NW, WM, TM, TN, NB, ST, LW, EPI, SPLIT, RL>;
+            else return &k_gemm_8p<TM, EPI, SPLIT>;
+        }
+    };
+};
+
+// the one dispatch: f(Tile<...>{}) for a kept configuration, false for any other id
+template <class F>
+static bool with_cfg(int cfg, F&& f) {
+    switch (cfg) {
+#define X(id, name, fam, nw, wm, tm, tnw, st, lw, rl, rope) \
+    case id: return f(Tile<fam, nw, wm, tm, tnw, st, lw, rl, rope>{});
+        PGMI_GEMM_CFGS(X)
+#undef X
+        default: return false;
+    }
+}
+
+bool gemm_cfg_valid(int cfg) {
+    return with_cfg(cfg, [](auto) { return true; });
+}
 
 struct Plan {
     Cfg cfg;
@@ -1290,17 +1187,27 @@ int gemm_force_shape(int M, int N, int K, int dual, int cfg, int split) {
         }
     if (cfg < 0) return 0;
     if (g_n_shape_plans >= 16) return -1;
-    g_shape_plans[g_n_shape_plans++] = {M, N, K, dual != 0, cfg, split < 1 ? 1 : split};
+    g_shape_plans[g_n_shape_plans++] = {M, N, K, dual != 0, cfg, split};
     return 0;
 }
 
 static Plan choose(int M, int N, int K, bool dual) {
-    if (g_force_cfg >= 0) {
-        static const int bms[] = {288, 288, 256, 256, 128, 128, 288, 256, 352, 288, 256, 128, 288, 256, 64, 128, 64, 128, 64, 128, 288, 352, 256, 288, 64, 64, 32, 64, 96, 96, 288, 288, 64, 352, 128, 128, 256, 192, 288};
-        static const int bns[] = {64, 32, 64, 32, 128, 64, 128, 128, 128, 64, 64, 128, 32, 32, 64, 64, 128, 128, 64, 64, 128, 128, 128, 256, 64, 64, 64, 32, 64, 64, 128, 64, 64, 128, 128, 64, 256, 256, 128};
-        const int c = g_force_cfg;
-        const int bn = (dual && c >= P288w) ? bns[c] / 2 : bns[c];
-        return {(Cfg)c, bms[c], bn, dual && c < P288w ? 1 : (g_force_split > 0 ? g_force_split : 1)};
+    // every plan -- forced, per-shape override, table, fallback -- is made here; a dual GEMM never splits
+    // (its two accumulators have no partial-slab form)
+    auto mk = [&](int c, int split) -> Plan {
+        Plan p{(Cfg)c, 0, 0, dual || split < 1 ? 1 : split};
+        with_cfg(c, [&](auto t) {
+            using T = decltype(t);
+            p.bm = T::BM;
+            p.bn = dual ? T::template For<EPI_GEGLU>::BN : T::template For<EPI_STORE>::BN;
+            return true;
+        });
+        return p;
+    };
+    if (g_force_cfg >= 0) return mk(g_force_cfg, g_force_split);
+    for (int i = 0; i < g_n_shape_plans; ++i) {
+        const ShapePlan& o = g_shape_plans[i];
+        if (o.M == M && o.N == N && o.K == K && o.dual == dual) return mk(o.cfg, o.split);
     }
     // Measured on MI355X (tools/gemm_sweep.py; GPU time of graph-replayed calls, round 1): the
     // PaliGemma prefill shapes at 224 px (M = 256 vision / 288 text rows) and 448 px (1024 /
@@ -1349,13 +1256,6 @@ static Plan choose(int M, int N, int K, bool dual) {
         {2304, 16384, 2048, true, E256, 1},     // text gate|up         261.8 us (W288w 301.8); in situ LM 10064 -> 9435 us
         {2304, 2048, 16384, false, W288w, 2},   // text down            153.9 us (was 298.6)
     };
-    static const int bms[] = {288, 288, 256, 256, 128, 128, 288, 256, 352, 288, 256, 128, 288, 256, 64, 128, 64, 128, 64, 128, 288, 352, 256, 288, 64, 64, 32, 64, 96, 96, 288, 288, 64, 352, 128, 128, 256, 192, 288};
-    static const int bns[] = {64, 32, 64, 32, 128, 64, 128, 128, 128, 64, 64, 128, 32, 32, 64, 64, 128, 128, 64, 64, 128, 128, 128, 256, 64, 64, 64, 32, 64, 64, 128, 64, 64, 128, 128, 64, 256, 256, 128};
-    auto mk = [&](Cfg c, int split) -> Plan { return {c, bms[c], dual ? bns[c] / 2 : bns[c], dual ? 1 : split}; };
-    for (int i = 0; i < g_n_shape_plans; ++i) {
-        const ShapePlan& o = g_shape_plans[i];
-        if (o.M == M && o.N == N && o.K == K && o.dual == dual) return mk((Cfg)o.cfg, o.split);
-    }
     for (const Entry& e : table)
         if (e.M == M && e.N == N && e.K == K && e.dual == dual) return mk(e.cfg, e.split);
     // lock-step decode batches as GEMMs (M <= 16 rows; tools/gemm_sweep.py b8_*
@@ -1370,10 +1270,18 @@ static Plan choose(int M, int N, int K, bool dual) {
     const long t64 = (long)((M + 63) / 64) * ((N + 63) / 64);
     if (t64 <= 256) return mk(P64x64, 1);
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    Plan p = mk(P128w, 1);
     const int nkt = (K + 63) / 64;
-    while (t128 * p.split < 200 && p.split < 4 && nkt / (p.split * 2) >= 4) p.split *= 2;
-    return p;
+    int split = 1;
+    while (t128 * split < 200 && split < 4 && nkt / (split * 2) >= 4) split *= 2;
+    return mk(P128w, split);
+}
+
+void gemm_plan(int M, int N, int K, int dual, int* cfg, int* bm, int* bn, int* split) {
+    const Plan p = choose(M, N, K, dual != 0);
+    *cfg = p.cfg;
+    *bm = p.bm;
+    *bn = p.bn;
+    *split = p.split;
 }
 
 size_t gemm_ws_bytes(int M, int N, int K) {
@@ -1443,232 +1351,58 @@ void gemm_probe_events(hipEvent_t start, hipEvent_t stop) {
     g_probe_ev0 = start;
     g_probe_ev1 = stop;
 }
-#define PGMI_GEMM_LAUNCH(KERN, GRID, BLOCK, LDS, S, ...)                                                  \
-    do {                                                                                                \
-        if (g_probe_ev0) {                                                                              \
-            hipExtLaunchKernelGGL(KERN, GRID, BLOCK, LDS, S, g_probe_ev0, g_probe_ev1, 0, __VA_ARGS__); \
-            g_probe_ev0 = g_probe_ev1 = nullptr;                                                        \
-        } else {                                                                                        \
-            hipLaunchKernelGGL(KERN, GRID, BLOCK, LDS, S, __VA_ARGS__);                                 \
-        }                                                                                               \
-    } while (0)
 
-template <int WGM, int WGN, int TM, int TN, int EPI>
-static void launch_t(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
-                     const EpiArgs& ea, float* ws, int split, long up_off) {
-    constexpr int NB = (EPI == EPI_GEGLU) ? 2 : 1;  // EPI < 0: partials only
-    constexpr int BM = WGM * TM * 16, BN = WGN * TN * 16, NT = 64 * WGM * WGN;
-    const size_t lds = (size_t)(2 * BM * LDSK + 2 * NB * BN * LDSK) * sizeof(uint16_t);
-    const int nkt = (K + BK - 1) / BK;
-    const int per = (nkt + split - 1) / split;
-    dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, split);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if constexpr (EPI >= 0)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm<WGM, WGN, TM, TN, EPI, false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm<WGM, WGN, TM, TN, EPI_STORE, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    if constexpr (EPI < 0) {
-        PGMI_GEMM_LAUNCH((k_gemm<WGM, WGN, TM, TN, EPI_STORE, true>), grid, dim3(NT), lds, s, A, lda, W, ldw, M, N,
-                           K, per, ea, ws, up_off);
-        return;
-    } else if (split == 1) {
-        PGMI_GEMM_LAUNCH((k_gemm<WGM, WGN, TM, TN, EPI, false>), grid, dim3(NT), lds, s, A, lda, W, ldw, M, N, K,
-                           per, ea, ws, up_off);
-    } else {
-        PGMI_GEMM_LAUNCH((k_gemm<WGM, WGN, TM, TN, EPI_STORE, true>), grid, dim3(NT), lds, s, A, lda, W, ldw, M, N,
-                           K, per, ea, ws, up_off);
-        long total4 = ((long)M * N + 3) / 4;
-        long blocks = (total4 + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL((k_splitk_epi<EPI>), dim3((unsigned)blocks), dim3(256), 0, s, ws, split, M, N, ea);
-    }
-}
-
-#undef PGMI_LDS_AT
-
-// panel GEMM launcher: WM x (4/WM) waves, TNW = 16-column fragments per wave (per B operand
-// for plain GEMMs; the dual GEMM splits them over gate and up); EPI < 0: partials only
-template <int NW, int WM, int TM, int TNW, int ST, int EPI>
-static void launch_p(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
-                     const EpiArgs& ea, float* ws, int split, long up_off) {
-    constexpr bool DUAL = (EPI == EPI_GEGLU);
-    constexpr int NB = DUAL ? 2 : 1;
-    constexpr int TN = DUAL ? (TNW >= 2 ? TNW / 2 : 1) : TNW;  // the dual GEMM keeps the B rows per slot
-    constexpr int BM = WM * TM * 16, BN = (NW / WM) * TN * 16;
-    constexpr int STQ = (size_t)ST * (BM + NB * BN) * 128 <= 163840 ? ST : ST - 1;  // fit 160 KiB
-    constexpr size_t lds = (size_t)STQ * (BM + NB * BN) * 128;
-    static_assert(lds <= 163840, "LDS ring exceeds 160 KiB");
-    constexpr int EK = EPI < 0 ? EPI_STORE : EPI;
+// The one launcher.  split > 1 (or partials: the deferred form, whose consumer kernel reduces the slabs) runs
+// the configuration's split kernel -- it never reaches an epilogue, so there is one instance per configuration
+// (EPI_STORE's) -- and, unless partials, k_splitk_epi<EPI>.  The dual and RoPE forms have no partial-slab form.
+template <class T, int EPI>
+static void launch(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
+                   const EpiArgs& ea, float* ws, int split, long up_off, bool partials) {
+    using E = typename T::template For<EPI>;
+    using S = typename T::template For<EPI_STORE>;
+    constexpr bool CAN_SPLIT = EPI != EPI_GEGLU && EPI != EPI_ROPE;
+    constexpr auto kern = E::template kernel<false>();
+    constexpr auto kern_split = S::template kernel<true>();
     const int nkt = (K + 63) / 64;
     const int per = (nkt + split - 1) / split;
-    const int n_mt = (M + BM - 1) / BM, n_nt = (N + BN - 1) / BN;
-    dim3 grid(n_mt * n_nt, split);
-    const int code = xcd_block(n_mt, n_nt, split, BM, NB * BN, K);
+    const int n_mt = (M + T::BM - 1) / T::BM, n_nt = (N + E::BN - 1) / E::BN;
+    const dim3 grid(n_mt * n_nt, split), block(T::THREADS);
+    int code = xcd_block(n_mt, n_nt, split, T::BM, E::NB * E::BN, K);
+    if (T::FAM == FAM_W && n_mt == 1) code |= 1 << 30;  // k_gemm_w: one row tile, the weights stream non-temporal
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_p<NW, WM, TM, TN, NB, STQ, EK, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_p<NW, WM, TM, TN, NB, STQ, EK, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)E::LDS);
+        if constexpr (CAN_SPLIT)
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern_split),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS);
         attr_set = true;
     }
-    if (EPI < 0 || split > 1) {
-        PGMI_GEMM_LAUNCH((k_gemm_p<NW, WM, TM, TN, NB, STQ, EK, true>), grid, dim3(64 * NW), lds, s, A, lda, W, ldw, M, N, K, per,
-                           ea, ws, up_off, n_mt, code);
-        if (EPI >= 0) {
-            long total4 = ((long)M * N + 3) / 4;
-            long blocks = (total4 + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL((k_splitk_epi<EK>), dim3((unsigned)blocks), dim3(256), 0, s, ws, split, M, N, ea);
+    auto run = [&](auto k, size_t lds) {
+        if (g_probe_ev0) {
+            hipExtLaunchKernelGGL(k, grid, block, lds, s, g_probe_ev0, g_probe_ev1, 0, A, lda, W, ldw, M, N, K, per, ea,
+                                  ws, up_off, n_mt, code);
+            g_probe_ev0 = g_probe_ev1 = nullptr;
+        } else {
+            hipLaunchKernelGGL(k, grid, block, lds, s, A, lda, W, ldw, M, N, K, per, ea, ws, up_off, n_mt, code);
         }
-    } else {
-        PGMI_GEMM_LAUNCH((k_gemm_p<NW, WM, TM, TN, NB, STQ, EK, false>), grid, dim3(64 * NW), lds, s, A, lda, W, ldw, M, N, K,
-                           per, ea, ws, up_off, n_mt, code);
-    }
-}
-
-// warp-specialised launcher: as launch_p, NW compute waves (grid WM x NW/WM) + LW loader waves (RL: in-wave reload)
-template <int NW, int WM, int TM, int TNW, int ST, int LW, int EPI, bool RL = false>
-static void launch_w(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
-                     const EpiArgs& ea, float* ws, int split, long up_off) {
-    constexpr bool DUAL = (EPI == EPI_GEGLU);
-    constexpr int NB = DUAL ? 2 : 1;
-    constexpr int TN = DUAL ? (TNW >= 2 ? TNW / 2 : 1) : TNW;
-    constexpr int BM = WM * TM * 16, BN = (NW / WM) * TN * 16;
-    constexpr size_t lds = (size_t)ST * (BM + NB * BN) * 128;
-    static_assert(lds <= 163840, "LDS ring exceeds 160 KiB");
-    constexpr int EK = EPI < 0 ? EPI_STORE : EPI;
-    const int nkt = (K + 63) / 64;
-    const int per = (nkt + split - 1) / split;
-    const int n_mt = (M + BM - 1) / BM, n_nt = (N + BN - 1) / BN;
-    dim3 grid(n_mt * n_nt, split);
-    const int code = xcd_block(n_mt, n_nt, split, BM, NB * BN, K) | (n_mt == 1 ? 1 << 30 : 0);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_w<NW, WM, TM, TN, NB, ST, LW, EK, false, RL>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_w<NW, WM, TM, TN, NB, ST, LW, EK, true, RL>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    const dim3 block(64 * (NW + LW));
-    if (EPI < 0 || split > 1) {
-        PGMI_GEMM_LAUNCH((k_gemm_w<NW, WM, TM, TN, NB, ST, LW, EK, true, RL>), grid, block, lds, s, A, lda, W, ldw, M, N, K,
-                           per, ea, ws, up_off, n_mt, code);
-        if (EPI >= 0) {
-            long total4 = ((long)M * N + 3) / 4;
-            long blocks = (total4 + 255) / 256;
+    };
+    if constexpr (CAN_SPLIT) {
+        if (partials || split > 1) {
+            run(kern_split, S::LDS);
+            if (partials) return;
+            long blocks = (((long)M * N + 3) / 4 + 255) / 256;
             if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL((k_splitk_epi<EK>), dim3((unsigned)blocks), dim3(256), 0, s, ws, split, M, N, ea);
+            hipLaunchKernelGGL((k_splitk_epi<EPI>), dim3((unsigned)blocks), dim3(256), 0, s, ws, split, M, N, ea);
+            return;
         }
-    } else {
-        PGMI_GEMM_LAUNCH((k_gemm_w<NW, WM, TM, TN, NB, ST, LW, EK, false, RL>), grid, block, lds, s, A, lda, W, ldw, M, N, K,
-                           per, ea, ws, up_off, n_mt, code);
     }
-}
-
-// 8-phase launcher (K % 64 == 0); EPI < 0: partials only
-template <int TM, int EPI>
-static void launch_8p(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
-                      const EpiArgs& ea, float* ws, int split, long up_off) {
-    constexpr bool DUAL = (EPI == EPI_GEGLU);
-    constexpr int BM = 32 * TM, BNO = DUAL ? 128 : 256;
-    constexpr size_t lds = (size_t)2 * (2 * 16 * TM * 128 + 2 * 128 * 128);
-    static_assert(lds <= 163840, "LDS exceeds 160 KiB");
-    constexpr int EK = EPI < 0 ? EPI_STORE : EPI;
-    const int nkt = K / 64;
-    const int per = (nkt + split - 1) / split;
-    const int n_mt = (M + BM - 1) / BM, n_nt = (N + BNO - 1) / BNO;
-    dim3 grid(n_mt * n_nt, split);
-    const int code = xcd_block(n_mt, n_nt, split, BM, DUAL ? 2 * BNO : BNO, K);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_8p<TM, EK, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_8p<TM, EK, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    if (EPI < 0 || split > 1) {
-        PGMI_GEMM_LAUNCH((k_gemm_8p<TM, EK, true>), grid, dim3(512), lds, s, A, lda, W, ldw, M, N, K, per, ea, ws,
-                           up_off, n_mt, code);
-        if (EPI >= 0) {
-            long total4 = ((long)M * N + 3) / 4;
-            long blocks = (total4 + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL((k_splitk_epi<EK>), dim3((unsigned)blocks), dim3(256), 0, s, ws, split, M, N, ea);
-        }
-    } else {
-        PGMI_GEMM_LAUNCH((k_gemm_8p<TM, EK, false>), grid, dim3(512), lds, s, A, lda, W, ldw, M, N, K, per, ea, ws,
-                           up_off, n_mt, code);
-    }
-}
-
-template <int EPI>
-static void launch_pcfg(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
-                        const EpiArgs& ea, float* ws, const Plan& p, long up_off) {
-#define P_(wm, tm, tn, st) launch_p<4, wm, tm, tn, st, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off)
-#define P8_(wm, tm, tn, st) launch_p<8, wm, tm, tn, st, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off)
-    switch (p.cfg) {
-        case P288w: P_(2, 9, 4, 3); break;
-        case P256w: P_(2, 8, 4, 3); break;
-        case P352w: P_(2, 11, 4, 2); break;
-        case P288n: P_(2, 9, 2, 3); break;
-        case P256n: P_(2, 8, 2, 4); break;
-        case P128w: P_(2, 4, 4, 3); break;
-        case P288t: P_(2, 9, 1, 4); break;
-        case P256t: P_(4, 4, 2, 4); break;
-        case P64x64: P_(2, 2, 2, 6); break;
-        case P128x64: P_(2, 4, 2, 6); break;
-        case P64x128: P_(2, 2, 4, 6); break;
-        case P128x128: P_(2, 4, 4, 5); break;
-        case P64x64d: P_(2, 2, 2, 10); break;
-        case P128x64d: P_(4, 2, 4, 6); break;
-        case Q288w: P8_(2, 9, 2, 3); break;
-        case Q352w: P8_(2, 11, 2, 2); break;
-        case Q256w: P8_(2, 8, 2, 3); break;
-        case Q288x256: P8_(2, 9, 4, 2); break;
-        case P64x64s3: P_(2, 2, 2, 3); break;
-        case P64x64s4: P_(2, 2, 2, 4); break;
-        case P32x64s4: P_(2, 1, 2, 4); break;
-        case P64x32s4: P_(2, 2, 1, 4); break;
-        case P96x64s4: P_(2, 3, 2, 4); break;
-        case P96x64s3: P_(2, 3, 2, 3); break;
-        case W288w: launch_w<8, 2, 9, 2, 3, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case W288n: launch_w<8, 2, 9, 1, 3, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case W64x64: launch_w<4, 2, 2, 2, 6, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case W352w: launch_w<8, 2, 11, 2, 2, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case W128x128: launch_w<8, 2, 4, 2, 4, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case W128x64: launch_w<4, 2, 4, 2, 5, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case E256: launch_8p<8, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case E192: launch_8p<6, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case R288w: launch_w<8, 2, 9, 2, 3, 4, EPI, true>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        default: break;
-    }
-#undef P_
-#undef P8_
-}
-
-template <int EPI>
-static void launch_e(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
-                     const EpiArgs& ea, float* ws, const Plan& p, long up_off) {
-    switch (p.cfg) {
-        case C288x64: launch_t<6, 1, 3, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case C288x32: launch_t<6, 1, 3, 2, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case C256x64: launch_t<4, 1, 4, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case C256x32: launch_t<4, 1, 4, 2, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case C128x128: launch_t<2, 2, 4, 4, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        case C128x64: launch_t<2, 2, 4, 2, EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-        default: launch_pcfg<EPI>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-    }
+    run(kern, E::LDS);
 }
 
 int gemm(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K, Epi epi,
          const EpiArgs& ea, float* ws, size_t ws_bytes, int up_offset_rows, bool defer) {
+    if (epi == EPI_ROPE) return 0;  // gemm_qkv_rope only
     Plan p = choose(M, N, K, epi == EPI_GEGLU);
     if ((p.cfg == E256 || p.cfg == E192) && K % 64 != 0) p.cfg = P128w;  // the 8-phase kernel has no K tail
     if (p.split > 1 && (size_t)p.split * M * N * sizeof(float) > ws_bytes) p.split = 1;
@@ -1683,31 +1417,20 @@ int gemm(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, 
         const int per = (nkt + p.split - 1) / p.split;
         p.split = (nkt + per - 1) / per;
     }
-    if (defer && p.split > 1) {
-        // partial slabs only: the consumer kernel (splitk_res_norm / rope_kv_append) reduces them
-        switch (p.cfg) {
-            case C288x64: launch_t<6, 1, 3, 4, -1>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-            case C288x32: launch_t<6, 1, 3, 2, -1>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-            case C256x64: launch_t<4, 1, 4, 4, -1>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-            case C256x32: launch_t<4, 1, 4, 2, -1>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-            case C128x128: launch_t<2, 2, 4, 4, -1>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-            case C128x64: launch_t<2, 2, 4, 2, -1>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off); break;
-            default: launch_pcfg<-1>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
+    // partial slabs only: the consumer kernel (splitk_res_norm / rope_kv_append) reduces them
+    const bool partials = defer && p.split > 1;
+    with_cfg(p.cfg, [&](auto t) {
+        using T = decltype(t);
+        switch (epi) {
+#define E_(e) case e: launch<T, e>(s, A, lda, W, ldw, M, N, K, ea, ws, p.split, up_off, partials); break;
+            E_(EPI_STORE) E_(EPI_BIAS) E_(EPI_BIAS_GELU) E_(EPI_BIAS_RES) E_(EPI_RES) E_(EPI_BIAS_POS) E_(EPI_F32)
+            E_(EPI_GEGLU)
+#undef E_
+            default: break;
         }
-        return p.split;
-    }
-    switch (epi) {
-        case EPI_STORE: launch_e<EPI_STORE>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-        case EPI_BIAS: launch_e<EPI_BIAS>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-        case EPI_BIAS_GELU: launch_e<EPI_BIAS_GELU>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-        case EPI_BIAS_RES: launch_e<EPI_BIAS_RES>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-        case EPI_RES: launch_e<EPI_RES>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-        case EPI_BIAS_POS: launch_e<EPI_BIAS_POS>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-        case EPI_F32: launch_e<EPI_F32>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-        case EPI_GEGLU: launch_e<EPI_GEGLU>(s, A, lda, W, ldw, M, N, K, ea, ws, p, up_off); break;
-        case EPI_ROPE: return 0;  // gemm_qkv_rope only
-    }
-    return 1;
+        return true;
+    });
+    return partials ? p.split : 1;
 }
 
 bool gemm_qkv_rope(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
@@ -1715,28 +1438,11 @@ bool gemm_qkv_rope(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W,
     if (N % 256 != 0 || N != (ea.nh + 2 * ea.nkv) * 256) return false;
     const Plan p = choose(M, N, K, false);
     if (p.split != 1) return false;
-    // configurations with two 16-column tiles per wave and a tile width dividing 256
-#define P_(wm, tm, st) launch_p<4, wm, tm, 2, st, EPI_ROPE>(s, A, lda, W, ldw, M, N, K, ea, nullptr, 1, 0)
-#define W_(nw, tm, st) launch_w<nw, 2, tm, 2, st, 4, EPI_ROPE>(s, A, lda, W, ldw, M, N, K, ea, nullptr, 1, 0)
-    switch (p.cfg) {
-        case P288n: P_(2, 9, 3); break;
-        case P64x64: P_(2, 2, 6); break;
-        case P128x64: P_(2, 4, 6); break;
-        case P64x64s3: P_(2, 2, 3); break;
-        case P64x64s4: P_(2, 2, 4); break;
-        case P32x64s4: P_(2, 1, 4); break;
-        case P96x64s4: P_(2, 3, 4); break;
-        case P96x64s3: P_(2, 3, 3); break;
-        case W288w: W_(8, 9, 3); break;
-        case W64x64: W_(4, 2, 6); break;
-        case W352w: W_(8, 11, 2); break;
-        case W128x128: W_(8, 4, 4); break;
-        case W128x64: launch_w<4, 2, 4, 2, 5, 4, EPI_ROPE>(s, A, lda, W, ldw, M, N, K, ea, nullptr, 1, 0); break;
-        default: return false;
-    }
-#undef P_
-#undef W_
-    return true;
+    return with_cfg(p.cfg, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (T::ROPE) launch<T, EPI_ROPE>(s, A, lda, W, ldw, M, N, K, ea, nullptr, 1, 0, false);
+        return T::ROPE;
+    });
 }
 
 // host replica of a launch's tile order (pgmi_debug_gemm_tiles: the CPU test that every workgroup of the

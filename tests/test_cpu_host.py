@@ -58,6 +58,90 @@ def test_gemm_tile_order_is_a_permutation(n_mt, n_nt, S, BM, BN, K, blocked):
     assert np.array_equal(np.sort(flat), np.arange(G))
 
 
+GEMM_KEPT_CFGS = (11, 14, 16, 22, 25, 26, 27, 28, 30, 31, 32, 33, 34, 36, 37, 38)
+# (M, N, K, dual, cfg, bm, bn, split): the plans of the commit before the dispatch became one configuration list,
+# dumped from its choose() (bm / bn from its bms[] / bns[] arrays)
+GEMM_PLANS = [
+    # every row of choose()'s table
+    (288, 2560, 2048, 0, 32, 64, 64, 1),
+    (288, 2048, 2048, 0, 34, 128, 128, 4),
+    (288, 16384, 2048, 1, 38, 288, 64, 1),
+    (288, 2048, 16384, 0, 31, 288, 64, 8),
+    (256, 3456, 1152, 0, 25, 64, 64, 1),
+    (256, 1152, 1152, 0, 25, 64, 64, 3),
+    (256, 4304, 1152, 0, 28, 96, 64, 1),
+    (256, 1152, 4304, 0, 28, 96, 64, 4),
+    (256, 1152, 640, 0, 27, 64, 32, 1),
+    (256, 2048, 1152, 0, 26, 32, 64, 1),
+    (1056, 2560, 2048, 0, 34, 128, 128, 1),
+    (1056, 2048, 2048, 0, 34, 128, 128, 1),
+    (1056, 16384, 2048, 1, 37, 192, 128, 1),
+    (1056, 2048, 16384, 0, 37, 192, 256, 5),
+    (1024, 3456, 1152, 0, 34, 128, 128, 1),
+    (1024, 1152, 1152, 0, 28, 96, 64, 1),
+    (1024, 4304, 1152, 0, 30, 288, 128, 1),
+    (1024, 1152, 4304, 0, 34, 128, 128, 3),
+    (2048, 3456, 1152, 0, 30, 288, 128, 1),
+    (2048, 1152, 1152, 0, 34, 128, 128, 1),
+    (2048, 4304, 1152, 0, 33, 352, 128, 1),
+    (2048, 1152, 4304, 0, 30, 288, 128, 2),
+    (2048, 2048, 1152, 0, 34, 128, 128, 1),
+    (2304, 2560, 2048, 0, 22, 256, 128, 1),
+    (2304, 2048, 2048, 0, 31, 288, 64, 1),
+    (2304, 16384, 2048, 1, 36, 256, 128, 1),
+    (2304, 2048, 16384, 0, 30, 288, 128, 2),
+    # the fallback rules
+    (8, 16384, 2048, 1, 16, 64, 64, 1),
+    (8, 2048, 16384, 0, 14, 64, 64, 8),
+    (8, 2048, 2048, 0, 14, 64, 64, 1),
+    (8, 2560, 2048, 0, 14, 64, 64, 1),
+    (320, 16384, 2048, 1, 33, 352, 64, 1),
+    (1200, 16384, 2048, 1, 33, 352, 64, 1),
+    (2100, 16384, 2048, 1, 30, 288, 64, 1),
+    (320, 2048, 16384, 0, 30, 288, 128, 4),
+    (600, 2048, 16384, 0, 30, 288, 128, 4),
+    (2100, 2048, 16384, 0, 30, 288, 128, 2),
+    (37, 200, 64, 0, 14, 64, 64, 1),
+    (1, 128, 2048, 0, 14, 64, 64, 1),
+    (320, 2560, 2048, 0, 14, 64, 64, 1),
+    (576, 2560, 2048, 0, 11, 128, 128, 2),
+    (512, 1152, 1152, 0, 14, 64, 64, 1),
+    (288, 257216, 2048, 0, 11, 128, 128, 1),
+]
+
+
+def _gemm_plan(lib, M, N, K, dual):
+    out = [ctypes.c_int() for _ in range(4)]
+    assert lib.pgmi_debug_gemm_plan(M, N, K, dual, *[ctypes.byref(o) for o in out]) == 0
+    return tuple(o.value for o in out)
+
+
+def test_gemm_plans_are_pinned():
+    """pgmi_debug_gemm_plan (what kernels_gemm.hip choose() returns): the measured table and every fallback rule
+    give the plans they gave before the dispatch was derived from one configuration list, tile sizes included; the
+    tuning hook takes the kept configuration ids and no other; a forced dual GEMM never splits."""
+    from pgmi import _native as N
+    lib = N.lib()
+    try:
+        assert lib.pgmi_tune_gemm(-1, 0) == 0
+        for M, Nn, K, dual, cfg, bm, bn, split in GEMM_PLANS:
+            assert _gemm_plan(lib, M, Nn, K, dual) == (cfg, bm, bn, split), (M, Nn, K, dual)
+        assert {p[4] for p in GEMM_PLANS} <= set(GEMM_KEPT_CFGS)
+        for cfg in range(-1, 48):
+            ok = cfg < 0 or cfg in GEMM_KEPT_CFGS
+            assert lib.pgmi_tune_gemm(cfg, 1) == (0 if ok else N.PGMI_E_ARG), cfg
+            assert lib.pgmi_tune_gemm_shape(5, 8, 64, 0, cfg, 1) == (0 if ok else N.PGMI_E_ARG), cfg
+            assert lib.pgmi_tune_gemm_shape(5, 8, 64, 0, -1, 0) == 0
+        for cfg in GEMM_KEPT_CFGS:
+            assert lib.pgmi_tune_gemm(cfg, 4) == 0
+            assert _gemm_plan(lib, 353, 192, 1024, 1)[0::3] == (cfg, 1)
+            assert _gemm_plan(lib, 353, 192, 1024, 0)[0::3] == (cfg, 4)
+    finally:
+        assert lib.pgmi_tune_gemm(-1, 0) == 0
+        lib.pgmi_tune_gemm_shape(5, 8, 64, 0, -1, 0)
+    assert _gemm_plan(lib, 288, 2048, 2048, 0) == (34, 128, 128, 4)
+
+
 def test_create_validates_config_without_gpu():
     """pgmi_create only builds the weight layout (no device memory): it runs here."""
     from pgmi import _native as N

@@ -303,3 +303,57 @@ def test_gemm_8phase(eng, cfg, M, N, K, epi, split):
     finally:
         NN.check(eng.lib.pgmi_tune_gemm(-1, 0))
     assert rel_l2(got, ref) < tol
+
+
+GEMM_CFGS = (11, 14, 16, 22, 25, 26, 27, 28, 30, 31, 32, 33, 34, 36, 37, 38)  # kernels_gemm.hip PGMI_GEMM_CFGS
+GEMM_DUAL_CFGS = (16, 30, 33, 36, 37, 38)     # what choose() can return for the dual gate|up GEMM
+# the smallest shapes a panel kernel can still go wrong at
+GEMM_EVERY_CFG_CASES = [
+    (37, 200, 64, "store", 1),         # one k-tile (a prologue shorter than every ring), ragged rows, a column
+                                       # guard inside a fragment
+    (300, 384, 1096, "bias_res", 1),   # K tail of 8 past 17 tiles, rows past one 288 / 256 tile (the 8-phase ids
+                                       # take gemm()'s P128w fallback here, as in production)
+    (520, 256, 2048, "res", 3),        # uneven K ranges through the fixed-order reduction (36 / 37: test_gemm_8phase)
+]
+GEMM_EVERY_CFG = ([c + (cfg,) for cfg in GEMM_CFGS for c in GEMM_EVERY_CFG_CASES
+                   if not (cfg in (36, 37) and c[3] == "res")] +
+                  [(353, 192, 1024, "geglu", 1, cfg) for cfg in GEMM_DUAL_CFGS])
+_every_cfg_data = {}
+
+
+def _gemm_every_cfg_data(M, N, K, epi):
+    """inputs and oracle output of one shape, shared by the configurations forced on it"""
+    key = (M, N, K, epi)
+    if key not in _every_cfg_data:
+        rng = np.random.default_rng(M + N + K)
+        A = rand(rng, M, K)
+        if epi == "geglu":
+            Wg, Wu = rand(rng, N, K, scale=2 / np.sqrt(K)), rand(rng, N, K, scale=2 / np.sqrt(K))
+            ref = O.bf16(O.gelu_tanh(O.bf16(A @ Wg.T)) * O.bf16(A @ Wu.T))
+            _every_cfg_data[key] = (A, np.concatenate([Wg, Wu]), None, None, ref)
+        else:
+            Wt, r, b = rand(rng, N, K, scale=1 / np.sqrt(K)), rand(rng, M, N), rand(rng, N, scale=0.1)
+            acc = A @ Wt.T
+            ref = {"store": lambda: O.bf16(acc), "res": lambda: O.bf16(O.bf16(acc) + r),
+                   "bias_res": lambda: O.bf16(O.bf16(acc + b) + r)}[epi]()
+            _every_cfg_data[key] = (A, Wt, b, r, ref)
+    return _every_cfg_data[key]
+
+
+@pytest.mark.parametrize("M,N,K,epi,split,cfg", GEMM_EVERY_CFG)
+def test_gemm_every_cfg(eng, cfg, M, N, K, epi, split):
+    """Every tile configuration of kernels_gemm.hip's list -- panel, warp-specialised, 8-phase -- forced through
+    the tuning hook at a short-K, a K-tail and a split-K shape, and the dual GeGLU GEMM on the configurations
+    choose() returns for it (with test_gemm_8phase: no configuration is left out)."""
+    from pgmi import _native as NN
+    from pgmi._native import EPI
+    A, Wt, b, r, ref = _gemm_every_cfg_data(M, N, K, epi)
+    NN.check(eng.lib.pgmi_tune_gemm(cfg, split))
+    try:
+        if epi == "geglu":
+            got = _gemm(eng, bf(A), bf(Wt), 7, geglu=True)
+        else:
+            got = _gemm(eng, bf(A), bf(Wt), EPI[epi], bias=bf(b), res=bf(r))
+    finally:
+        NN.check(eng.lib.pgmi_tune_gemm(-1, 0))
+    assert rel_l2(got, ref) < (5e-3 if epi == "geglu" else 3e-3)

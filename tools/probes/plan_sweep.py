@@ -19,8 +19,8 @@ sys.path.insert(0, os.path.join(REPO, "multimodal-financial-analysis-tool-using-
 from pgmi import Engine, _native as N  # noqa: E402
 from pgmi.synthetic import init_policy, paligemma_3b_config  # noqa: E402
 
-CFGS = [14, 15, 17, 24, 25, 26, 27, 28, 29, 32, 34, 35]
-CFGS_LM = [6, 7, 9, 11, 17, 20, 22, 30, 31, 33, 34, 35]
+CFGS = [14, 25, 26, 27, 28, 32, 34]
+CFGS_LM = [11, 22, 30, 31, 33, 34]
 
 
 def time_tower(eng, px, iters):
