@@ -48,7 +48,8 @@ typedef struct pgmi_config {
     int projection_dim;
     int64_t image_token_index;
     int64_t pad_token_id; /* -1 when the config's pad_token_id is None (modeling_gemma.py:453) */
-    int max_batch;        /* sequences / images per call                                    */
+    int max_batch;        /* sequences / images per call, in [1, 16] (the decode MFMA tile's rows;
+                           * a prefill of more than 8 runs as row groups of 8)               */
     int max_seq;          /* longest prefill (image + text tokens)                          */
     int max_kv;           /* KV-cache capacity in tokens (decode attention scratch)          */
 } pgmi_config;
@@ -169,7 +170,7 @@ int pgmi_lm_forward_ragged(pgmi_ctx* ctx, const int64_t* ids, const void* image_
  * and the token record work as pgmi_decode / pgmi_decode_steps: logits holds the last step's, next_ids
  * (required when n_steps > 1) every step's argmax in turn, tokens (may be NULL) [n_steps][B].
  * Nothing at or past a row's own length is read.  PGMI_E_ARG: a row with
- * kv_lens[b] + n_steps > kv_max, B over capacity, null arrays. */
+ * kv_lens[b] + n_steps > kv_max, B over capacity (max_batch, at most 16), null arrays. */
 int pgmi_decode_ragged(pgmi_ctx* ctx, const int64_t* ids, int B, void* kv, int kv_batch, int kv_max,
                        const int32_t* kv_lens, const int32_t* positions, int n_steps, float* logits, int64_t* next_ids,
                        int64_t* tokens, int use_graph, void* stream);
@@ -351,7 +352,7 @@ int pgmi_op_rope(pgmi_ctx* ctx, const void* x, const void* cos_rows, const void*
                  int head_dim, void* out, void* stream);
 /* out = bf16(x * a) over n bf16 values (n a multiple of 8): GemmaModel's normalizer (modeling_gemma.py:367-368) */
 int pgmi_op_scale(pgmi_ctx* ctx, const void* x, float a, int64_t n, void* out, void* stream);
-/* decode GEMV family on one layer's weights (tests): y[b][n] += W x (residual form) */
+/* decode GEMV family on one layer's weights (tests): y[b][n] += W x (residual form); B in [1, 16], K 2048 or 16384 */
 int pgmi_op_gemv_res(pgmi_ctx* ctx, const void* x, const void* W, int B, int N, int K, void* h_inout,
                      void* stream);
 

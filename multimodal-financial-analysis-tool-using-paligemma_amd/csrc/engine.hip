@@ -28,6 +28,11 @@ using namespace pgmi;
 
 static thread_local std::string g_err;
 
+// Prefill (vision tower, projector, language-model forward) runs at most this many images / sequences per pass: a
+// larger batch goes through as row groups, each at a GEMM shape whose plans were measured (M = 8 x 256 / 288 rows),
+// inside the 64 MiB split-K workspace, and with results that do not depend on the batch the group came in.
+constexpr int kPrefillGroup = 8;
+
 static int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
@@ -39,8 +44,17 @@ static int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(PGMI_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// a launcher's own refusal (launch_error_set): reported like a failed launch
+static int launcher_error() {
+    const char* what = "";
+    const hipError_t e = pgmi::launch_error_take(&what);
+    if (e == hipSuccess) return 0;
+    return fail(PGMI_E_HIP, std::string("kernel launch: ") + what + ": " + hipGetErrorString(e));
+}
+
 #define LAUNCHCHK()                                                                        \
     do {                                                                                   \
+        if (int r_ = launcher_error()) return r_;                                          \
         hipError_t e_ = hipGetLastError();                                                 \
         if (e_ != hipSuccess) return fail(PGMI_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
     } while (0)
@@ -97,12 +111,13 @@ struct pgmi_ctx {
     int kpad = 0;
     uint16_t* cosT = nullptr;
     uint16_t* sinT = nullptr;
-    // text prefill workspace (rows = max_batch*max_seq)
+    // text prefill workspace (Hs, Tn, dpos, dids_tmp: max_batch*max_seq rows; the per-layer scratch QKV, Qr, AO, ACT:
+    // one prefill group's, min(max_batch, 8)*max_seq rows)
     uint16_t *Hs, *Tn, *QKV, *Qr, *AO, *ACT, *lastrows;
     long tn_rows = 0;  // rows of Tn holding the final RMSNorm of the last pgmi_lm_forward (pgmi_lm_final_hidden)
     int64_t* dpos;
     int64_t* dids_tmp;
-    // vision workspace (rows = max_batch*N)
+    // vision workspace (one prefill group's rows: min(max_batch, 8)*N)
     uint16_t *vX, *vT, *vQKV, *vAO, *vH, *vP;
     float* ws;
     size_t ws_bytes;
@@ -120,7 +135,7 @@ struct pgmi_ctx {
     StepState* step;
     StepState* pstep;  // the generate-loop prefill's last-row attention (flash-decoding over the prompt's keys)
     StepState* rstep;  // the ragged step's records, one per batch row ([max_batch], pgmi_decode_ragged)
-    int* d_rlens;      // ragged prefill: [0, 8) each row's token count, [8, 16) its attended key count
+    int* d_rlens;      // ragged prefill: [0, 16) each row's token count, [16, 32) its attended key count
     int64_t* d_ids;
     uint16_t* d_emb;             // staged input rows of pgmi_decode_embeds ([max_batch][hidden] bf16)
     float* d_mask;               // staged additive decode mask ([max_batch][max_kv] fp32, pgmi_decode_embeds_dev)
@@ -140,7 +155,7 @@ struct pgmi_ctx {
     // the same for the ragged step's per-row records (rows [0, rstep_B))
     bool rstep_known = false;
     int rstep_B = 0;
-    int rstep_kv[8] = {0}, rstep_pos[8] = {0};
+    int rstep_kv[kMaxRows] = {0}, rstep_pos[kMaxRows] = {0};
     // in-situ timing probe of the prefill MLP GEMMs (pgmi_prefill_probe): events around layer i's gate|up
     // GEMM (ev[4i], ev[4i+1]) and down GEMM (ev[4i+2], ev[4i+3]) of eager forwards
     std::vector<hipEvent_t> probe_ev;
@@ -320,6 +335,9 @@ void build_rope_host(pgmi_ctx* x, std::vector<uint16_t>& cs, std::vector<uint16_
 }
 
 int ensure_prepared(pgmi_ctx* x) {
+    // the entry of every compute call: a launcher error that an earlier call on this thread left untaken (a path
+    // without a launch check) is that call's, not this one's
+    (void)pgmi::launch_error_take(nullptr);
     if (!x->prepared) return fail(PGMI_E_STATE, "pgmi_prepare() has not been called");
     if (!x->slab) return fail(PGMI_E_STATE, "weights are not bound (pgmi_bind_weights)");
     return 0;
@@ -425,7 +443,7 @@ int pgmi_create(int device, const pgmi_config* cfg, pgmi_ctx** out) {
     if (c.v_hidden % c.v_heads != 0 || c.v_hidden / c.v_heads != 72) return fail(PGMI_E_ARG, "SigLIP head_dim must be 72");
     if (c.t_kv_heads != 1 || c.t_heads > 8)
         return fail(PGMI_E_ARG, "decode path is specialised for MQA with <= 8 query heads (num_key_value_heads = 1)");
-    if (c.max_batch < 1 || c.max_batch > 8) return fail(PGMI_E_ARG, "max_batch must be in [1, 8]");
+    if (c.max_batch < 1 || c.max_batch > kMaxRows) return fail(PGMI_E_ARG, "max_batch must be in [1, 16]");
     if (c.v_hidden > 4096) return fail(PGMI_E_ARG, "v_hidden too large for the LayerNorm kernel");
     auto* x = new pgmi_ctx();
     x->c = c;
@@ -656,7 +674,10 @@ int pgmi_prepare(pgmi_ctx* x) {
     int rc;
     if (!x->cosT) {
         const int N = n_img(c);
-        const size_t R = (size_t)c.max_batch * c.max_seq, RV = (size_t)c.max_batch * N;
+        // R: every row of a batch (the hidden state, its norm, positions); RG / RV: one prefill group's rows, all that
+        // the per-layer scratch and the vision workspace ever hold at a time
+        const size_t R = (size_t)c.max_batch * c.max_seq, RG = (size_t)std::min(c.max_batch, kPrefillGroup) * c.max_seq,
+                     RV = (size_t)std::min(c.max_batch, kPrefillGroup) * N;
         const int H = c.t_hidden, QKVN = (c.t_heads + 2 * c.t_kv_heads) * c.t_head_dim;
         x->kpad = (c.v_channels * c.v_patch * c.v_patch + 63) / 64 * 64;
         if ((rc = dalloc_t(x, &x->patch_w, (size_t)c.v_hidden * x->kpad))) return rc;
@@ -664,10 +685,10 @@ int pgmi_prepare(pgmi_ctx* x) {
         if ((rc = dalloc_t(x, &x->sinT, (size_t)c.t_max_pos * c.t_head_dim / 2))) return rc;
         if ((rc = dalloc_t(x, &x->Hs, R * H))) return rc;
         if ((rc = dalloc_t(x, &x->Tn, R * H))) return rc;
-        if ((rc = dalloc_t(x, &x->QKV, R * QKVN))) return rc;
-        if ((rc = dalloc_t(x, &x->Qr, R * c.t_heads * c.t_head_dim))) return rc;
-        if ((rc = dalloc_t(x, &x->AO, R * H))) return rc;
-        if ((rc = dalloc_t(x, &x->ACT, R * c.t_intermediate))) return rc;
+        if ((rc = dalloc_t(x, &x->QKV, RG * QKVN))) return rc;
+        if ((rc = dalloc_t(x, &x->Qr, RG * c.t_heads * c.t_head_dim))) return rc;
+        if ((rc = dalloc_t(x, &x->AO, RG * H))) return rc;
+        if ((rc = dalloc_t(x, &x->ACT, RG * c.t_intermediate))) return rc;
         if ((rc = dalloc_t(x, &x->lastrows, (size_t)c.max_batch * H))) return rc;
         if ((rc = dalloc_t(x, &x->dpos, R))) return rc;
         if ((rc = dalloc_t(x, &x->dids_tmp, R))) return rc;
@@ -693,8 +714,8 @@ int pgmi_prepare(pgmi_ctx* x) {
         if ((rc = dalloc_t(x, &x->pidx, (size_t)B * gemv_logits_blocks()))) return rc;
         if ((rc = dalloc_t(x, &x->step, 1))) return rc;
         if ((rc = dalloc_t(x, &x->pstep, 1))) return rc;
-        if ((rc = dalloc_t(x, &x->rstep, 8))) return rc;
-        if ((rc = dalloc_t(x, &x->d_rlens, 16))) return rc;
+        if ((rc = dalloc_t(x, &x->rstep, kMaxRows))) return rc;
+        if ((rc = dalloc_t(x, &x->d_rlens, 2 * kMaxRows))) return rc;
         if ((rc = dalloc_t(x, &x->amax_v, (size_t)argmax_scratch_parts()))) return rc;
         if ((rc = dalloc_t(x, &x->amax_i, (size_t)argmax_scratch_parts()))) return rc;
         if ((rc = dalloc_t(x, &x->d_ids, (size_t)B))) return rc;
@@ -749,8 +770,18 @@ int pgmi_vision(pgmi_ctx* x, const void* pixels, int dtype, int B, void* feats, 
     if (B < 1 || B > c.max_batch) return fail(PGMI_E_ARG, "batch exceeds max_batch");
     if (!pixels || !feats) return fail(PGMI_E_ARG, "null argument");
     const std::vector<intptr_t> key{1, (intptr_t)pixels, dtype, B, (intptr_t)feats};
-    rc = run_prefill(x, (hipStream_t)stream, key,
-                     [&](hipStream_t st) { return vision_body(x, st, pixels, dtype, B, feats); });
+    // more than kPrefillGroup images: row groups of that many, one after the other through the same workspace, each
+    // with the plans measured for it -- an image's features do not depend on how many images share the call
+    const size_t px_img = (size_t)c.v_channels * c.v_image * c.v_image * (dtype == PGMI_DTYPE_F32 ? 4 : 2);
+    const size_t ft_img = (size_t)n_img(c) * c.v_hidden * sizeof(uint16_t);
+    rc = run_prefill(x, (hipStream_t)stream, key, [&](hipStream_t st) {
+        for (int b0 = 0; b0 < B; b0 += kPrefillGroup) {
+            const int r = vision_body(x, st, reinterpret_cast<const char*>(pixels) + b0 * px_img, dtype,
+                                      std::min(kPrefillGroup, B - b0), reinterpret_cast<char*>(feats) + b0 * ft_img);
+            if (r) return r;
+        }
+        return 0;
+    });
     if (rc) return rc;
     LAUNCHCHK();
     return 0;
@@ -820,8 +851,13 @@ int pgmi_project(pgmi_ctx* x, const void* feats, int rows, void* out, void* stre
     e.bias = x->w.proj_b;
     e.out = reinterpret_cast<uint16_t*>(out);
     e.ldo = x->c.projection_dim;
-    gemm((hipStream_t)stream, reinterpret_cast<const uint16_t*>(feats), x->c.v_hidden, x->w.proj_w, x->c.v_hidden, rows,
-         x->c.projection_dim, x->c.v_hidden, EPI_BIAS, e, x->ws, x->ws_bytes);
+    const int grp = kPrefillGroup * n_img(x->c);  // row groups of kPrefillGroup images, as pgmi_vision
+    for (int r0 = 0; r0 < rows; r0 += grp) {
+        e.out = reinterpret_cast<uint16_t*>(out) + (size_t)r0 * x->c.projection_dim;
+        gemm((hipStream_t)stream, reinterpret_cast<const uint16_t*>(feats) + (size_t)r0 * x->c.v_hidden, x->c.v_hidden,
+             x->w.proj_w, x->c.v_hidden, std::min(grp, rows - r0), x->c.projection_dim, x->c.v_hidden, EPI_BIAS, e, x->ws,
+             x->ws_bytes);
+    }
     LAUNCHCHK();
     return 0;
 }
@@ -840,6 +876,8 @@ int pgmi_embed(pgmi_ctx* x, const int64_t* ids, int rows, void* out, void* strea
 static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
                    const void* embeds, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
                    int logits_rows, bool ragged);
+static int lm_rows(pgmi_ctx* x, hipStream_t s, int b0, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start,
+                   float* logits, int logits_rows, bool ragged);
 
 static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows, const void* embeds,
                       int B, int L, const int64_t* positions, const int32_t* lens, bool ragged, void* kv, int kv_batch,
@@ -908,10 +946,7 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
     const pgmi_config& c = x->c;
     // ragged: row b holds lens[b] tokens (d_rlens, set outside the graph), the rest of its L slots is padding
     const int* rlens = ragged ? x->d_rlens : nullptr;
-    const int* rkeys = ragged ? x->d_rlens + 8 : nullptr;
-    const int H = c.t_hidden, R = B * L, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
-    const int QKVN = (NH + 2 * NKV) * HD;
-    const float eps = c.t_rms_eps;
+    const int H = c.t_hidden, R = B * L;
     const float normalizer = bf16_round_host(std::sqrt((float)H));  // torch.tensor(H**0.5, dtype=bf16) (:367)
     const uint16_t* E = x->w.embed;
     if (embeds) {
@@ -921,13 +956,38 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
                     c.image_token_index, c.pad_token_id, (float)std::sqrt((double)H), normalizer, nullptr,
                     reinterpret_cast<int*>(x->dids_tmp), x->Hs, rlens);
     }
+    // the layers: row groups of at most kPrefillGroup sequences, one after the other (the merge above ran for the
+    // whole batch: the k-th <image> token of the batch takes image row k); a group's rows of Hs / Tn, its positions,
+    // lengths, KV rows and logits are its slice of the batch's, everything else is scratch that the groups share
+    for (int b0 = 0; b0 < B; b0 += kPrefillGroup) {
+        const int r = lm_rows(x, s, b0, std::min(kPrefillGroup, B - b0), L, kv, kv_batch, kv_max, kv_start, logits,
+                              logits_rows, ragged);
+        if (r) return r;
+    }
+    return 0;
+}
+
+static int lm_rows(pgmi_ctx* x, hipStream_t s, int b0, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start,
+                   float* logits, int logits_rows, bool ragged) {
+    const pgmi_config& c = x->c;
+    const int* rlens = ragged ? x->d_rlens + b0 : nullptr;
+    const int* rkeys = ragged ? x->d_rlens + kMaxRows + b0 : nullptr;
+    const int H = c.t_hidden, R = B * L, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
+    const int QKVN = (NH + 2 * NKV) * HD;
+    const float eps = c.t_rms_eps;
+    const uint16_t* E = x->w.embed;
+    uint16_t* const Hs = x->Hs + (size_t)b0 * L * H;
+    uint16_t* const Tn = x->Tn + (size_t)b0 * L * H;
+    uint16_t* const lastrows = x->lastrows + (size_t)b0 * H;
+    const int64_t* const dpos = x->dpos + (size_t)b0 * L;
+    logits += (size_t)b0 * (logits_rows == 0 ? L : 1) * c.t_vocab;
     const long kvd = (long)NKV * HD, kvb = (long)kv_max * kvd;
-    uint16_t* kvp = reinterpret_cast<uint16_t*>(kv);
+    uint16_t* kvp = reinterpret_cast<uint16_t*>(kv) + (long)b0 * kvb;  // the group's rows of every layer's K and V
     const uint16_t* fnorm = x->w.final_norm;
     const bool last_only = logits_rows == 2 && L > 1 && c.t_layers > 0;
     // input RMSNorm of layer 0; every later RMSNorm (and the final norm) is fused with the
     // preceding projection's split-K reduction + residual (splitk_res_norm)
-    rmsnorm(s, x->Hs, c.t_layers ? x->w.t[0].in_norm : fnorm, eps, x->Tn, R, H);
+    rmsnorm(s, Hs, c.t_layers ? x->w.t[0].in_norm : fnorm, eps, Tn, R, H);
     for (int i = 0; i < c.t_layers; ++i) {
         const TextLayerW& w = x->w.t[i];
         uint16_t* Kc = kvp + ((long)(i * 2 + 0) * kv_batch) * kvb;
@@ -935,12 +995,12 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
         EpiArgs q{};
         q.out = x->QKV; q.ldo = QKVN;
         // RoPE + KV append in the projection's epilogue where the shape's plan allows it
-        q.rpos = x->dpos; q.cosT = x->cosT; q.sinT = x->sinT; q.max_pos = c.t_max_pos;
+        q.rpos = dpos; q.cosT = x->cosT; q.sinT = x->sinT; q.max_pos = c.t_max_pos;
         q.q_out = x->Qr; q.kc = Kc; q.vc = Vc; q.kv_b_stride = kvb; q.kv_start = kv_start;
         q.L = L; q.nh = NH; q.nkv = NKV;
-        if (HD != 256 || !gemm_qkv_rope(s, x->Tn, H, w.qkv, H, R, QKVN, H, q)) {
-            int sp = gemm(s, x->Tn, H, w.qkv, H, R, QKVN, H, EPI_STORE, q, x->ws, x->ws_bytes, 0, true);
-            rope_kv_append(s, x->QKV, x->ws, sp, B, L, NH, NKV, x->dpos, x->cosT, x->sinT, c.t_max_pos, x->Qr, Kc, Vc,
+        if (HD != 256 || !gemm_qkv_rope(s, Tn, H, w.qkv, H, R, QKVN, H, q)) {
+            int sp = gemm(s, Tn, H, w.qkv, H, R, QKVN, H, EPI_STORE, q, x->ws, x->ws_bytes, 0, true);
+            rope_kv_append(s, x->QKV, x->ws, sp, B, L, NH, NKV, dpos, x->cosT, x->sinT, c.t_max_pos, x->Qr, Kc, Vc,
                            kvb, kv_start);
         }
         AttnArgs a{};
@@ -961,7 +1021,7 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
             a.q = x->Qr + (size_t)(L - 1) * NH * HD;
             a.o = x->dAO; a.o_b_stride = (long)H;
             a.Lq = 1;
-            HIPCHK(hipMemcpy2DAsync(x->lastrows, (size_t)H * 2, x->Hs + (size_t)(L - 1) * H, (size_t)L * H * 2,
+            HIPCHK(hipMemcpy2DAsync(lastrows, (size_t)H * 2, Hs + (size_t)(L - 1) * H, (size_t)L * H * 2,
                                     (size_t)H * 2, B, hipMemcpyDeviceToDevice, s));
             if (kv_start + L <= c.max_kv) {
                 // one query row over the prompt's keys: the decode step's flash-decoding (64-key chunks
@@ -972,47 +1032,47 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
                 HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&x->pstep->kv_len), kv_start + L - 1, 1, s));
                 a.mask = x->d_zero; a.mask_b_stride = 0; a.mask_k_stride = 0; a.mask_round = 1;
                 attention_decode(s, a, x->pstep, kv_start + L, x->opart, x->max_chunks);
-                gemv_o_attn(s, B, NH, x->opart, x->max_chunks, x->pstep, w.o, H, x->lastrows,
+                gemv_o_attn(s, B, NH, x->opart, x->max_chunks, x->pstep, w.o, H, lastrows,
                             B >= gemv_mf_min_batch() ? x->dAO : nullptr);
             } else {
                 attention_prefill(s, 256, a);
-                gemv_res(s, B, NH * HD, x->dAO, w.o, H, x->lastrows, x->ws);
+                gemv_res(s, B, NH * HD, x->dAO, w.o, H, lastrows, x->ws);
             }
-            gemv_geglu(s, B, x->lastrows, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT);
-            gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->lastrows, x->ws);
+            gemv_geglu(s, B, lastrows, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT);
+            gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, lastrows, x->ws);
             break;
         }
         attention_prefill(s, 256, a);
         EpiArgs o{};
-        o.res = x->Hs; o.ldr = H; o.out = x->Hs; o.ldo = H;
+        o.res = Hs; o.ldr = H; o.out = Hs; o.ldo = H;
         int sp = gemm(s, x->AO, H, w.o, H, R, H, NH * HD, EPI_RES, o, x->ws, x->ws_bytes, 0, true);
-        splitk_res_norm(s, x->ws, sp, nullptr, x->Hs, w.post_norm, nullptr, eps, x->Tn, R, H);
+        splitk_res_norm(s, x->ws, sp, nullptr, Hs, w.post_norm, nullptr, eps, Tn, R, H);
         EpiArgs g{};
         g.out = x->ACT; g.ldo = c.t_intermediate;
         const bool probe = x->probe_on && (size_t)(4 * i + 3) < x->probe_ev.size();
         // probe: the GEMM kernel itself carries the events (its own start / end, gemm_probe_events)
         if (probe) gemm_probe_events(x->probe_ev[4 * i], x->probe_ev[4 * i + 1]);
-        gemm(s, x->Tn, H, w.gate_up, H, R, c.t_intermediate, H, EPI_GEGLU, g, x->ws, x->ws_bytes, c.t_intermediate);
+        gemm(s, Tn, H, w.gate_up, H, R, c.t_intermediate, H, EPI_GEGLU, g, x->ws, x->ws_bytes, c.t_intermediate);
         EpiArgs d{};
-        d.res = x->Hs; d.ldr = H; d.out = x->Hs; d.ldo = H;
+        d.res = Hs; d.ldr = H; d.out = Hs; d.ldo = H;
         if (probe) gemm_probe_events(x->probe_ev[4 * i + 2], x->probe_ev[4 * i + 3]);
         sp = gemm(s, x->ACT, c.t_intermediate, w.down, c.t_intermediate, R, H, c.t_intermediate, EPI_RES, d, x->ws,
                   x->ws_bytes, 0, true);
         const bool last = i + 1 == c.t_layers;
-        splitk_res_norm(s, x->ws, sp, nullptr, x->Hs, last ? fnorm : x->w.t[i + 1].in_norm, nullptr, eps, x->Tn, R, H);
+        splitk_res_norm(s, x->ws, sp, nullptr, Hs, last ? fnorm : x->w.t[i + 1].in_norm, nullptr, eps, Tn, R, H);
     }
     if (logits_rows == 0) {
         EpiArgs l{};  // Tn holds the final RMSNorm (modeling_gemma.py:379)
         l.out_f32 = logits; l.ldo = c.t_vocab;
-        gemm(s, x->Tn, H, E, H, R, c.t_vocab, H, EPI_F32, l, x->ws, x->ws_bytes);
+        gemm(s, Tn, H, E, H, R, c.t_vocab, H, EPI_F32, l, x->ws, x->ws_bytes);
     } else {
         if (ragged)  // each row's last real token, lens[b] - 1
-            gather_last_rows(s, x->Hs, B, L, H, rlens, x->lastrows);
+            gather_last_rows(s, Hs, B, L, H, rlens, lastrows);
         else if (!last_only)
-            HIPCHK(hipMemcpy2DAsync(x->lastrows, (size_t)H * 2, x->Hs + (size_t)(L - 1) * H, (size_t)L * H * 2,
+            HIPCHK(hipMemcpy2DAsync(lastrows, (size_t)H * 2, Hs + (size_t)(L - 1) * H, (size_t)L * H * 2,
                                     (size_t)H * 2, B, hipMemcpyDeviceToDevice, s));
         int nparts = 0;
-        gemv_logits(s, B, x->lastrows, fnorm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts);
+        gemv_logits(s, B, lastrows, fnorm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts);
     }
     LAUNCHCHK();
     return 0;
@@ -1094,7 +1154,7 @@ static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, vo
     if (!gemv_logits(s, B, x->dH, x->w.final_norm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts, x->lm_done, nx,
                      st, hist, adv_n))
         argmax_finish(s, B, x->pmax, x->pidx, nparts, nx, st, hist, adv_n);
-    return 0;
+    return launcher_error();  // (inside a capture too: a step with a launch missing is never instantiated)
 }
 
 int pgmi_prefill_probe(pgmi_ctx* x, int on) {
@@ -1319,7 +1379,7 @@ int pgmi_decode_ragged(pgmi_ctx* x, const int64_t* ids, int B, void* kv, int kv_
                        int64_t* tokens, int use_graph, void* stream) {
     if (!ids || !kv_lens || !positions) return fail(PGMI_E_ARG, "null argument");
     if (n_steps > 1 && !next_ids) return fail(PGMI_E_ARG, "multi-step decode: next_ids carries the token fed back");
-    if (x && (B < 1 || B > x->c.max_batch || B > 8)) return fail(PGMI_E_ARG, "batch exceeds capacity");
+    if (x && (B < 1 || B > x->c.max_batch || B > kMaxRows)) return fail(PGMI_E_ARG, "batch exceeds capacity");
     return decode_step(x, ids, nullptr, B, kv, kv_batch, kv_max, 0, 0, logits, next_ids, use_graph, stream, nullptr,
                        n_steps, tokens, kv_lens, positions);
 }
@@ -1501,7 +1561,8 @@ int pgmi_prefill_kernel(pgmi_ctx* x, int which, int layer, int rows, void* strea
     int rc;
     if ((rc = ensure_prepared(x))) return rc;
     const pgmi_config& c = x->c;
-    if (rows < 1 || rows > c.max_batch * c.max_seq) return fail(PGMI_E_ARG, "rows exceed the prefill workspace");
+    if (rows < 1 || rows > std::min(c.max_batch, kPrefillGroup) * c.max_seq)
+        return fail(PGMI_E_ARG, "rows exceed the prefill workspace (one group of 8 sequences)");
     if (layer < 0 || layer >= c.t_layers) return fail(PGMI_E_ARG, "layer out of range");
     hipStream_t s = (hipStream_t)stream;
     const int H = c.t_hidden;
@@ -1747,9 +1808,9 @@ int pgmi_op_scale(pgmi_ctx* x, const void* in, float a, int64_t n, void* out, vo
 int pgmi_op_gemv_res(pgmi_ctx* x, const void* in, const void* Wt, int B, int N, int K, void* h, void* stream) {
     if (!x) return fail(PGMI_E_ARG, "null ctx");
     if (K != 2048 && K != 16384) return fail(PGMI_E_ARG, "K must be 2048 or 16384");
-    if (B < 1 || B > 8) return fail(PGMI_E_ARG, "B must be in [1, 8]");
+    if (B < 1 || B > kMaxRows) return fail(PGMI_E_ARG, "B must be in [1, 16]");
     if (!x->ws) return fail(PGMI_E_STATE, "workspace not allocated (pgmi_prepare)");
-    if ((size_t)4 * B * N * sizeof(float) > x->ws_bytes) return fail(PGMI_E_ARG, "N too large for the scratch");
+    if ((size_t)(K / 2048) * B * N * sizeof(float) > x->ws_bytes) return fail(PGMI_E_ARG, "N too large for the scratch");
     gemv_res((hipStream_t)stream, B, K, reinterpret_cast<const uint16_t*>(in), reinterpret_cast<const uint16_t*>(Wt), N,
              reinterpret_cast<uint16_t*>(h), x->ws);
     LAUNCHCHK();

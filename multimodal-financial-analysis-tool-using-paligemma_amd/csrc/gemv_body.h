@@ -1,5 +1,6 @@
 #pragma once
-// gemv_body.h -- KV-cached decode projections (batch B <= 8 rows), gfx950.
+// gemv_body.h -- KV-cached decode projections (v_dot2 form: batch B <= 8 rows; 3..16 rows run on MFMA,
+// kernels_gemv_mfma.hip), gfx950.
 //
 // Decode at batch 1 streams ~5.02 GB of weights per token, so every
 // projection of GemmaDecoderLayer (modeling_gemma.py:307-338) is one HBM-bound pass over

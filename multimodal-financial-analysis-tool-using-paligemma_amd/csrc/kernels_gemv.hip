@@ -14,14 +14,35 @@ int gemv_mf_logits(hipStream_t s, const GemvArgs& a, int max_blocks);
 void gemv_mf_res(hipStream_t s, const GemvArgs& a, float* ws);
 void gemv_mf_res_norm(hipStream_t s, const GemvArgs& a, float* ws, const uint16_t* norm_w, float eps, uint16_t* hn);
 
+// a launcher's failed set-up, kept until the engine's next launch check takes it (one per thread, the first wins)
+static thread_local hipError_t g_launch_err = hipSuccess;
+static thread_local const char* g_launch_what = "";
+
+void launch_error_set(hipError_t e, const char* what) {
+    if (g_launch_err != hipSuccess) return;
+    g_launch_err = e;
+    g_launch_what = what;
+}
+
+hipError_t launch_error_take(const char** what) {
+    const hipError_t e = g_launch_err;
+    if (what) *what = g_launch_what;
+    g_launch_err = hipSuccess;
+    return e;
+}
+
 template <int B, int KCH, int RPW, int MODE, int WK = 1, int DEPTH = 1, bool EMB = false, bool RG = false>
 static void launch_gemv(hipStream_t s, const GemvArgs& a, int max_blocks = 0) {
     constexpr bool XREG = (MODE != GV_ORES) && B * (KCH / WK) <= 8;
     size_t lds = XREG ? 0 : (size_t)B * KCH * 512 * sizeof(uint16_t);
     static size_t attr = 0;  // largest dynamic LDS size granted so far
     if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            launch_error_set(e, "k_gemv: dynamic LDS size");
+            return;
+        }
         attr = lds;
     }
     constexpr int per_block = (4 / WK) * RPW;
@@ -73,7 +94,14 @@ void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W,
         if (B <= 1) L_(1, 4, 1, GV_RES);
         else if (B <= 2) L_(2, 4, 1, GV_RES);
         else if (B <= 4) L_(4, 4, 1, GV_RES);
-        else L_(8, 4, 1, GV_RES);
+        else if (B <= 8) L_(8, 4, 1, GV_RES);
+        else {  // 9..16 rows without the MFMA form's scratch: the 8-row kernel once per row group
+            for (int b0 = 0; b0 < B; b0 += 8) {
+                GemvArgs c = a;
+                c.x = x + (long)b0 * K; c.out = h_inout + (long)b0 * N; c.nb = (B - b0) < 8 ? (B - b0) : 8;
+                launch_gemv<8, 4, 1, GV_RES>(s, c);
+            }
+        }
     } else {  // K = 16384: x staged per <= 4 rows (LDS 32 KiB per row)
         for (int b0 = 0; b0 < B; b0 += 4) {
             const int nb = (B - b0) < 4 ? (B - b0) : 4;
@@ -121,7 +149,9 @@ void gemv_o_attn(hipStream_t s, int B, int G, const float* part, int max_chunks,
     else if (B <= 2 && st_stride != 0) launch_gemv<2, 4, 2, GV_ORES, 1, 1, false, true>(s, a, 256);
     else if (B <= 2) launch_gemv<2, 4, 2, GV_ORES>(s, a, 256);
     else if (B <= 4) launch_gemv<4, 4, 1, GV_ORES>(s, a, 256);
-    else launch_gemv<8, 4, 1, GV_ORES>(s, a, 256);
+    else if (B <= 8) launch_gemv<8, 4, 1, GV_ORES>(s, a, 256);
+    // 9..16 rows take the MFMA form above (the engine always passes o_out for B >= 3); this kernel holds 8
+    else launch_error_set(hipErrorInvalidValue, "gemv_o_attn: more than 8 rows need the o_out buffer");
 }
 
 void gemv_geglu(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w, float eps, const uint16_t* Wgu,

@@ -1,11 +1,13 @@
-// kernels_gemv_mfma.hip -- decode projections for 2..16 sequences in lock-step (BASELINE configs[3]:
-// 8 images per GPU), on MFMA.
+// kernels_gemv_mfma.hip -- decode projections for 3..16 sequences per step (BASELINE configs[3]:
+// 8 images per GPU; 16 fill the tile), on MFMA.
 //
 // At batch 1 a decode projection is one HBM pass with v_dot2 (gemv_body.h).  At batch B the
 // same pass owes B dot products per weight byte; on v_dot2 that turns the pass VALU-bound (B = 8:
 // gate/up 90 us vs 22 us at B = 1).  Here the batch rows are the M side of a v_mfma_f32_16x16x32_bf16
 // (rows >= B are zero) and 16 weight rows are the N side, so the pass is back to one read of
-// the weights:
+// the weights -- the same read for 3 rows as for 16.  No reduction involves the batch size (K splits, combine
+// order and the lanes' fragments are fixed), so a row's result is the same bits whatever batch it runs in
+// (tests/test_gpu_batch16.py):
 //   - one wave owns a 16-unit group (16 weight rows; 16 row pairs for RoPE / GeGLU) over a
 //     KW-wide slice of K; WK waves of a workgroup split K and meet in LDS; KS workgroups split
 //     it further for the 16384-wide down_proj (fp32 partial slabs, reduced by k_mf_combine);
@@ -24,6 +26,7 @@
 namespace pgmi {
 
 constexpr int MF_MAXB = 16;
+static_assert(MF_MAXB == kMaxRows, "a context's row capacity is the MFMA tile's M side");
 
 // RMSNorm'd (or plain) activation rows into xs (stride ld).  Every row's chunks are loaded
 // before any is reduced (one round trip for the whole [nb][K] block, not one per row).  NBM: rows
@@ -855,8 +858,12 @@ static void launch_mf(hipStream_t s, const GemvArgs& a, int blocks, int KS, floa
     const size_t lds = (MODE == GV_RES || NS) ? 0 : (size_t)a.nb * (a.K + 8) * sizeof(uint16_t);
     static size_t attr = 0;
     if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {  // not launched: the engine reports it with its launch errors
+            launch_error_set(e, "k_gemv_mf: dynamic LDS size");
+            return;
+        }
         attr = lds;
     }
     hipLaunchKernelGGL((k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG>), dim3(blocks, KS), dim3(64 * WK), lds, s, a, ws);
@@ -870,8 +877,12 @@ static void launch_ml(hipStream_t s, const GemvArgs& a, int blocks, int KS, floa
     const size_t lds = (((size_t)a.nb * (KSL + 8) * 2 + 127) & ~(size_t)127) + (size_t)waves * D * NR * 16 * 256;
     static size_t attr = 0;
     if (lds > attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_ml<MODE, NR, KSL, D>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_ml<MODE, NR, KSL, D>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {  // not launched: the engine reports it with its launch errors
+            launch_error_set(e, "k_gemv_ml: dynamic LDS size");
+            return;
+        }
         attr = lds;
     }
     hipLaunchKernelGGL((k_gemv_ml<MODE, NR, KSL, D>), dim3(blocks, KS), dim3(64 * waves), lds, s, a, ws);
@@ -960,7 +971,11 @@ int gemv_mf_logits(hipStream_t s, const GemvArgs& a, int max_blocks) {  // K = 2
     // (the register-streamed form at 512 / 1,024 / 2,048 workgroups measured no faster: 1.741-1.768 ms; again in
     // round 5 with the peeled loop: B = 8 step 1.283 -> 1.330-1.341 ms, profiles/r05_b8_lm_mf_ab.txt)
     const int blocks = ms_blocks(a.n_units, max_blocks < 256 ? max_blocks : 256);
-    launch_ml<GV_LOGITS, 1, 2048, 6>(s, a, blocks, 1, nullptr);
+    // 9..16 rows: a 5-deep ring.  The 6-deep one and 16 staged rows are 164,096 B of dynamic LDS, past the CU's
+    // 160 KiB; 5 slots make 147,712 B.  The ring's depth only changes when a k block is fetched, not the order the
+    // MFMAs accumulate them in, so a row's logits are the same bits under either instance.
+    if (a.nb > 8) launch_ml<GV_LOGITS, 1, 2048, 5>(s, a, blocks, 1, nullptr);
+    else launch_ml<GV_LOGITS, 1, 2048, 6>(s, a, blocks, 1, nullptr);
     return blocks;
 }
 
@@ -987,8 +1002,9 @@ void gemv_mf_res_norm(hipStream_t s, const GemvArgs& a, float* ws, const uint16_
 
 // residual projections; ws: fp32 scratch of KS x nb x N floats for the K split of K = 16384
 void gemv_mf_res(hipStream_t s, const GemvArgs& a, float* ws) {
-    if (a.K == 2048) {
-        launch_ml<GV_RES, 1, 2048, 6>(s, a, ms_blocks(a.n_units, 256), 1, nullptr);
+    if (a.K == 2048) {  // (9..16 rows: the 5-deep ring, as gemv_mf_logits)
+        if (a.nb > 8) launch_ml<GV_RES, 1, 2048, 5>(s, a, ms_blocks(a.n_units, 256), 1, nullptr);
+        else launch_ml<GV_RES, 1, 2048, 6>(s, a, ms_blocks(a.n_units, 256), 1, nullptr);
         return;
     }
     if (a.K % 2048 == 0 && ws) {  // K slices of 2048 over grid.y, fp32 partials, fixed-order combine

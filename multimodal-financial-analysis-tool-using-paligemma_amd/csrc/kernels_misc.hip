@@ -682,7 +682,7 @@ __global__ void k_set_step(StepState* st, int kv_len, int position) {
 // the ragged step's records, one per batch row, from the caller's host arrays (passed by value)
 __global__ void k_set_step_rows(StepState* st, RowInts kv_lens, RowInts positions, int B) {
     const int b = threadIdx.x;
-    if (b < B && b < 8) {
+    if (b < B && b < kMaxRows) {
         st[b].kv_len = kv_lens.v[b];
         st[b].position = positions.v[b];
     }
@@ -694,9 +694,9 @@ void set_step_rows(hipStream_t s, StepState* st, const RowInts& kv_lens, const R
 
 __global__ void k_set_row_ints(int* dst, RowInts a, RowInts b2, int B) {
     const int b = threadIdx.x;
-    if (b < B && b < 8) {
+    if (b < B && b < kMaxRows) {
         dst[b] = a.v[b];
-        dst[8 + b] = b2.v[b];
+        dst[kMaxRows + b] = b2.v[b];
     }
 }
 

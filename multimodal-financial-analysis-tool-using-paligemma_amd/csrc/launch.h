@@ -68,6 +68,11 @@ bool gemm_cfg_valid(int cfg);              // a tile configuration of kernels_ge
 void gemm_plan(int M, int N, int K, int dual, int* cfg, int* bm, int* bn, int* split);
 
 // ---------------------------------------------------------------- decode GEMV
+// A launcher that cannot launch (a kernel attribute the runtime refuses, a batch no kernel form covers) records
+// the error here and launches nothing; the engine's launch check takes it with the launch errors
+// (hipSuccess: none since the last take).
+void launch_error_set(hipError_t e, const char* what);
+hipError_t launch_error_take(const char** what);
 struct StepState {  // device-resident decode step (read by kernels -> graph-replayable)
     int kv_len;     // index the new token's K/V is written at (= KVCache.num_items())
     int position;   // rotary position (= attention_mask.cumsum(-1)[:, -1], modeling_gemma.py:526)
@@ -211,12 +216,14 @@ void merge_embed(hipStream_t s, const int64_t* ids, int B, int L, const uint16_t
                  const int* lens = nullptr);
 // out[b] = x[b][lens[b] - 1] (rows of D bf16, D % 8 == 0): each sequence's last real token of a ragged batch
 void gather_last_rows(hipStream_t s, const uint16_t* x, int B, int L, int D, const int* lens, uint16_t* out);
-// per-row host values handed to a setter kernel by value (B <= 8 rows, pgmi_create's max_batch bound): no
-// staging copy, and nothing of the host arrays is read after the launch call returns
-struct RowInts { int v[8]; };
+// sequences per context (pgmi_create's max_batch bound): the 16 rows of the batched decode projections' MFMA tile
+constexpr int kMaxRows = 16;
+// per-row host values handed to a setter kernel by value (B <= kMaxRows rows): no staging copy, and nothing of
+// the host arrays is read after the launch call returns
+struct RowInts { int v[kMaxRows]; };
 // the ragged step's per-row records: st[b] = {kv_lens.v[b], positions.v[b]}
 void set_step_rows(hipStream_t s, StepState* st, const RowInts& kv_lens, const RowInts& positions, int B);
-// dst[b] = a.v[b], dst[8 + b] = b2.v[b] (a ragged prefill's token counts and attended key counts)
+// dst[b] = a.v[b], dst[kMaxRows + b] = b2.v[b] (a ragged prefill's token counts and attended key counts)
 void set_row_ints(hipStream_t s, int* dst, const RowInts& a, const RowInts& b2, int B);
 void scale_rows(hipStream_t s, const uint16_t* x, long n, float normalizer, uint16_t* out);
 void add_rows(hipStream_t s, const uint16_t* x, const uint16_t* y, long n, uint16_t* out);  // bf16(x + y), n % 8 == 0

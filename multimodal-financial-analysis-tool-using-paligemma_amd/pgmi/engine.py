@@ -51,6 +51,8 @@ class Engine:
     GEN_CHUNK = 8
     GEN_MIN_BATCH = 3
 
+    # max_batch: sequences / images per call, 1..16 (16 rows fill the batched decode projections' MFMA tile: a B = 16
+    # step costs 5 % more than a B = 8 one, tools/probes/batch16_probe.py); the default stays 8
     def __init__(self, cfg, device=None, max_batch: int = 8, max_seq: int = 1472, max_kv: Optional[int] = None):
         self.lib = N.lib()
         self.cfgd = config_dict(cfg)
