@@ -213,6 +213,24 @@ int pgmi_set_decode_staged_norm(pgmi_ctx* ctx, int on);
  * Together with pgmi_lm_final_hidden this materialises the prefill's all-row logits on demand
  * after a last-row-only pgmi_lm_forward (SURVEY.md sec.7 hard part 3: lazy logits). */
 int pgmi_lm_head(pgmi_ctx* ctx, const void* normed, int rows, float* logits, void* stream);
+/* Token log-probabilities of the loss of PaliGemmaForConditionalGeneration.forward (modeling_gemma.py:596-603)
+ * over final-normed hidden rows, without materialising the logits: with logit[v] = fp32(bf16(normed . E[v])) --
+ * bit for bit pgmi_lm_head's whenever that GEMM runs unsplit (always at vocab 257216; a smaller vocabulary's
+ * fallback plan can split K at some row counts, and its sums then run in another order) -- lse = logsumexp(logit) and logprob[row] = logit[labels[row]] - lse.  labels: device
+ * int64 [rows] (the caller has applied the reference's shift); a row whose label is ignore_index gets 0 (the caller
+ * leaves it out of the mean), any other label outside [0, vocab) gets NaN and nothing is read out of bounds.
+ * logprob, lse (may be NULL): device fp32 [rows].  The lm_head GEMM's tiles reduce to (max, sum exp) pairs in the
+ * context's split-K workspace, rows in chunks that fit it; the order of every sum is fixed (two calls return the
+ * same bits).  Stream-ordered, no synchronisation.  PGMI_E_ARG: null pointers, rows < 1, or a forced GEMM
+ * configuration (pgmi_tune_gemm) without this epilogue; PGMI_E_STATE before pgmi_prepare. */
+int pgmi_lm_logprobs(pgmi_ctx* ctx, const void* normed, int rows, const int64_t* labels, int64_t ignore_index,
+                     float* logprob, float* lse, void* stream);
+/* The same rule (modeling_gemma.py:596-603) on logits that already exist -- the decode step's device fp32
+ * [rows][V]: lse (may be NULL) = logsumexp(logits[row]), logprob[row] = logits[row][ids[row]] - lse, 0 for
+ * ids[row] == ignore_index, NaN for any other id outside [0, V).  Stream-ordered, no synchronisation.  Scratch:
+ * the context's argmax scratch. */
+int pgmi_logprobs(pgmi_ctx* ctx, const float* logits, int rows, int V, const int64_t* ids, int64_t ignore_index,
+                  float* logprob, float* lse, void* stream);
 /* Copies the final RMSNorm output (GemmaModel.norm, modeling_gemma.py:379) of the B*L rows of the
  * last pgmi_lm_forward (bf16 [rows][hidden], row-major) into `out` (device memory). */
 int pgmi_lm_final_hidden(pgmi_ctx* ctx, void* out, int rows, void* stream);
@@ -311,6 +329,11 @@ int pgmi_sample_top_p(pgmi_ctx* ctx, const float* x, int rows, int V, float temp
  * 6 fp32 out (out is float*), 7 GeGLU with up rows at W + N*K */
 int pgmi_op_gemm(pgmi_ctx* ctx, const void* A, const void* W, int M, int N, int K, int epi, const void* bias,
                  const void* res, void* out, void* stream);
+/* pgmi_lm_logprobs (the loss of modeling_gemma.py:596-603) on a caller's W[V][K] (bf16, row-major) in place of the
+ * tied embedding: normed is [rows][K].  K a multiple of 8.  The logits it reduces are pgmi_op_gemm(epi 6)'s on the
+ * same operands, bit for bit, whenever that GEMM runs unsplit. */
+int pgmi_op_lm_logprobs(pgmi_ctx* ctx, const void* normed, const void* W, int rows, int V, int K,
+                        const int64_t* labels, int64_t ignore_index, float* logprob, float* lse, void* stream);
 /* pgmi_op_gemm with explicit row strides (elements, multiples of 8, >= K) of A and W: the prefill GEMMs'
  * sensitivity to the operands' row pitch (tools/probes/stride_probe.py). */
 int pgmi_op_gemm_strided(pgmi_ctx* ctx, const void* A, int lda, const void* W, int ldw, int M, int N, int K, int epi,

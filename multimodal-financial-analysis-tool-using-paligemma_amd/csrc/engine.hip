@@ -1423,6 +1423,55 @@ int pgmi_lm_head(pgmi_ctx* x, const void* normed, int rows, float* logits, void*
     return 0;
 }
 
+// The lm_head GEMM with the EPI_LSE epilogue + the combine, over row chunks whose tile pairs fit the split-K
+// workspace (pairs [chunk][column tiles] first, the label logits [chunk] behind them): nothing of rows x V is kept.
+static int lm_logprobs_run(pgmi_ctx* x, const void* normed, const uint16_t* W, int rows, int V, int K,
+                           const int64_t* labels, int64_t ignore_index, float* logprob, float* lse, void* stream) {
+    if (!x->ws) return fail(PGMI_E_STATE, "workspace not allocated (pgmi_prepare)");
+    if (V < 1 || K < 8 || K % 8 != 0) return fail(PGMI_E_ARG, "lm_logprobs: V >= 1 and K a positive multiple of 8");
+    // the narrowest column tile of an EPI_LSE configuration is 64 wide: a bound on the pairs per row for any plan
+    const size_t per_row = (size_t)((V + 63) / 64) * sizeof(float2) + sizeof(float);
+    const int per = (int)std::min<size_t>((size_t)rows, x->ws_bytes / per_row);
+    if (per < 1) return fail(PGMI_E_ARG, "lm_logprobs: vocabulary exceeds the scratch");
+    float2* part = reinterpret_cast<float2*>(x->ws);
+    float* lab = reinterpret_cast<float*>(reinterpret_cast<char*>(x->ws) + (size_t)per * (per_row - sizeof(float)));
+    const uint16_t* A = reinterpret_cast<const uint16_t*>(normed);
+    hipStream_t s = (hipStream_t)stream;
+    for (int r0 = 0; r0 < rows; r0 += per) {
+        const int nr = std::min(per, rows - r0);
+        const int n_nt = gemm_lse_tiles(nr, V, K);
+        if (n_nt < 1 || !gemm_lse(s, A + (size_t)r0 * K, K, W, K, nr, V, K, labels + r0, part, lab))
+            return fail(PGMI_E_ARG, "lm_logprobs: the forced GEMM configuration has no log-sum-exp epilogue");
+        lse_combine(s, part, n_nt, lab, labels + r0, nr, V, ignore_index, logprob + r0, lse ? lse + r0 : nullptr);
+    }
+    LAUNCHCHK();
+    return 0;
+}
+
+int pgmi_lm_logprobs(pgmi_ctx* x, const void* normed, int rows, const int64_t* labels, int64_t ignore_index,
+                     float* logprob, float* lse, void* stream) {
+    if (!x || !normed || !labels || !logprob) return fail(PGMI_E_ARG, "null argument");
+    if (rows < 1) return fail(PGMI_E_ARG, "lm_logprobs: no rows");
+    int rc;
+    if ((rc = ensure_prepared(x))) return rc;
+    return lm_logprobs_run(x, normed, x->w.embed, rows, x->c.t_vocab, x->c.t_hidden, labels, ignore_index, logprob, lse,
+                           stream);
+}
+
+int pgmi_logprobs(pgmi_ctx* x, const float* logits, int rows, int V, const int64_t* ids, int64_t ignore_index,
+                  float* logprob, float* lse, void* stream) {
+    if (!x || !logits || !ids || !logprob) return fail(PGMI_E_ARG, "null argument");
+    if (rows < 1 || V < 1) return fail(PGMI_E_ARG, "logprobs: empty logits");
+    if (!x->amax_v || !x->amax_i) return fail(PGMI_E_STATE, "logprobs scratch missing (pgmi_prepare)");
+    static_assert(sizeof(float) == sizeof(int), "the argmax index scratch holds the partial sums");
+    const int per = argmax_scratch_parts();
+    for (int r0 = 0; r0 < rows; r0 += per)  // row batches the scratch covers (stream-ordered)
+        logprob_rows((hipStream_t)stream, logits + (size_t)r0 * V, std::min(per, rows - r0), V, ids + r0, ignore_index,
+                     x->amax_v, reinterpret_cast<float*>(x->amax_i), logprob + r0, lse ? lse + r0 : nullptr);
+    LAUNCHCHK();
+    return 0;
+}
+
 int pgmi_lm_final_hidden(pgmi_ctx* x, void* out, int rows, void* stream) {
     int rc;
     if ((rc = ensure_prepared(x))) return rc;
@@ -1655,6 +1704,16 @@ int pgmi_op_gemm(pgmi_ctx* x, const void* A, const void* Wt, int M, int N, int K
          K, (Epi)epi, e, x->ws, x->ws_bytes, epi == EPI_GEGLU ? N : 0);
     LAUNCHCHK();
     return 0;
+}
+
+int pgmi_op_lm_logprobs(pgmi_ctx* x, const void* normed, const void* W, int rows, int V, int K, const int64_t* labels,
+                        int64_t ignore_index, float* logprob, float* lse, void* stream) {
+    if (!x || !normed || !W || !labels || !logprob) return fail(PGMI_E_ARG, "null argument");
+    if (rows < 1) return fail(PGMI_E_ARG, "lm_logprobs: no rows");
+    int rc;
+    if ((rc = ensure_prepared(x))) return rc;
+    return lm_logprobs_run(x, normed, reinterpret_cast<const uint16_t*>(W), rows, V, K, labels, ignore_index, logprob,
+                           lse, stream);
 }
 
 int pgmi_op_gemm_strided(pgmi_ctx* x, const void* A, int lda, const void* Wt, int ldw, int M, int N, int K, int epi,

@@ -244,6 +244,127 @@ __device__ __forceinline__ void rope_apply(const EpiArgs& ea, int M, int mb, int
         }
 }
 
+// EPI_LSE epilogue (k_gemm_p, k_gemm_w): the lm_head GEMM that keeps no logits.  x = rbf(acc) is the value EPI_F32
+// stores; columns n >= N count as -inf.  A wave reduces each of its rows over its TN x 16 columns to (m, s = sum
+// exp(x - m)) -- in-lane over j, then xor-shuffles over lane & 15 -- and the WN waves that share a row meet in LDS
+// (the ring's memory, free once every wave has left the k loop), merged in wave order: a fixed order, so a second
+// call returns the same bits.  The lane that holds column lse_labels[m] also stores that x to lse_lab[m].
+// lse_load reads the rows' labels before the k loop, from clamped addresses (see epi_load / rope_load); a label
+// outside [0, N) becomes -1, which no column matches.
+template <int TM>
+__device__ __forceinline__ void lse_load(const EpiArgs& ea, int M, int N, int mb, int lane, int (&lb)[TM][4]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            int m = mb + i * 16 + (lane >> 4) * 4 + r;
+            m = m < M ? m : M - 1;
+            const long l = ea.lse_labels[m];
+            lb[i][r] = (l >= 0 && l < N) ? (int)l : -1;
+        }
+}
+
+// sm: [WN][BM] pairs; rl0 = the wave's first row inside the tile
+template <int TM, int TN, int BM>
+__device__ __forceinline__ void lse_wave(const EpiArgs& ea, int M, int N, int mb, int nb, int rl0, int wn, int lane,
+                                         float2* sm, const f32x4 (&acc)[TM][TN], int (&lb)[TM][4]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            asm volatile("" : "+v"(lb[i][r]));
+            const int m = mb + i * 16 + (lane >> 4) * 4 + r;
+            float x[TN];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int n = nb + j * 16 + (lane & 15);
+                const float v = rbf(acc[i][j][r]);
+                x[j] = n < N ? v : -INFINITY;
+                mx = fmaxf(mx, x[j]);
+                if (n == lb[i][r] && m < M) ea.lse_lab[m] = v;  // lb < N: the column is a real one
+            }
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+            const float ms = mx == -INFINITY ? 0.f : mx;  // a wave whose columns are all past N: s = 0
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) s += expf(x[j] - ms);
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
+            if ((lane & 15) == 0) sm[wn * BM + rl0 + i * 16 + (lane >> 4) * 4 + r] = make_float2(mx, s);
+        }
+}
+
+template <int WN, int BM>
+__device__ __forceinline__ void lse_merge(const EpiArgs& ea, int M, int m0, int nt, const float2* sm, int tid,
+                                          int nthreads) {
+    for (int r = tid; r < BM; r += nthreads) {
+        const int m = m0 + r;
+        if (m >= M) continue;
+        float mx = sm[r].x;
+#pragma unroll
+        for (int w = 1; w < WN; ++w) mx = fmaxf(mx, sm[w * BM + r].x);
+        const float ms = mx == -INFINITY ? 0.f : mx;
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < WN; ++w) {
+            const float2 q = sm[w * BM + r];
+            s += q.y * expf(q.x - ms);
+        }
+        ea.lse_part[(long)m * ea.lse_nt + nt] = make_float2(mx, s);
+    }
+}
+
+// Each row's column-tile pairs merged in ascending tile order, in fp64 (one workgroup per row; thread 0 adds):
+// lse = M + log(sum_t s_t exp(m_t - M)), logprob = lab - lse (fp32, from the rounded lse).
+__global__ void __launch_bounds__(256) k_lse_combine(const float2* __restrict__ part, int n_nt,
+                                                     const float* __restrict__ lab, const int64_t* __restrict__ labels,
+                                                     int N, int64_t ignore_index, float* __restrict__ logprob,
+                                                     float* __restrict__ lse) {
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float2* p = part + (long)row * n_nt;
+    __shared__ float smax[256];
+    __shared__ double term[256];
+    float mx = -INFINITY;
+    for (int t = tid; t < n_nt; t += 256) mx = fmaxf(mx, p[t].x);
+    smax[tid] = mx;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) smax[tid] = fmaxf(smax[tid], smax[tid + o]);
+        __syncthreads();
+    }
+    const float Mx = smax[0];
+    const double Ms = Mx == -INFINITY ? 0.0 : (double)Mx;
+    double acc = 0.0;
+    for (int base = 0; base < n_nt; base += 256) {
+        const int t = base + tid;
+        term[tid] = t < n_nt ? (double)p[t].y * exp((double)p[t].x - Ms) : 0.0;
+        __syncthreads();
+        if (tid == 0) {
+            const int n = n_nt - base < 256 ? n_nt - base : 256;
+            for (int k = 0; k < n; ++k) acc += term[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float l = (float)((double)Mx + log(acc));
+        if (lse) lse[row] = l;
+        const int64_t lb = labels[row];
+        float lp;
+        if (lb == ignore_index) lp = 0.f;
+        else if (lb < 0 || lb >= N) lp = __builtin_nanf("");
+        else lp = lab[row] - l;
+        logprob[row] = lp;
+    }
+}
+
+void lse_combine(hipStream_t s, const float2* part, int n_nt, const float* lab, const int64_t* labels, int rows, int N,
+                 int64_t ignore_index, float* logprob, float* lse) {
+    hipLaunchKernelGGL(k_lse_combine, dim3(rows), dim3(256), 0, s, part, n_nt, lab, labels, N, ignore_index, logprob,
+                       lse);
+}
+
 // split-K reduction in fixed z order + epilogue (4 consecutive outputs per thread)
 template <int EPI>
 __global__ void k_splitk_epi(const float* __restrict__ ws, int S, int M, int N, EpiArgs ea) {
@@ -446,6 +567,8 @@ __global__ void __launch_bounds__(64 * NW, 1) k_gemm_p(const uint16_t* __restric
     if constexpr (!SPLIT) epi_load<EPI, TM, TN>(ea, M, N, epi_mb, epi_nb, lane, epi_ops);
     RopeOps<EPI == EPI_ROPE ? TM : 1> rope_ops;
     if constexpr (!SPLIT && EPI == EPI_ROPE) rope_load<TM, BN>(ea, M, epi_mb, epi_nb, lane, rope_ops);
+    int lse_lb[EPI == EPI_LSE ? TM : 1][4];
+    if constexpr (!SPLIT && EPI == EPI_LSE) lse_load<TM>(ea, M, N, epi_mb, lane, lse_lb);
 
     // ring: tiles t+1 .. t+ST-1 in flight or landed while tile t is multiplied.  Per tile:
     //   read kk=1 fragments | MFMAs kk=0 | retire tile t+1, barrier, refill the slot tile t
@@ -506,6 +629,12 @@ __global__ void __launch_bounds__(64 * NW, 1) k_gemm_p(const uint16_t* __restric
             }
     } else if constexpr (EPI == EPI_ROPE) {
         rope_apply<TM>(ea, M, epi_mb, lane, rope_ops, acc[0]);
+    } else if constexpr (EPI == EPI_LSE) {
+        float2* sm = reinterpret_cast<float2*>(smem_p);
+        __syncthreads();  // every wave has read its last fragments: the ring's memory is free
+        lse_wave<TM, TN, BM>(ea, M, N, epi_mb, epi_nb, wm * TM * 16, wn, lane, sm, acc[0], lse_lb);
+        __syncthreads();
+        lse_merge<WN, BM>(ea, M, m0, nt, sm, tid, 64 * NW);
     } else {
         epi_apply<EPI, TM, TN>(ea, M, N, epi_mb, epi_nb, lane, epi_ops, acc[0], acc[NB - 1]);
     }
@@ -619,6 +748,11 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_gemm_w(const uint16_t* __
             if (t + ST - 1 < nkt) issue(kt0 + t + ST - 1, slot_next);
             slot_next = slot_next + 1 == ST ? 0 : slot_next + 1;
         }
+        if constexpr (!SPLIT && EPI == EPI_LSE) {  // the compute waves' two epilogue barriers, then a share of the merge
+            __syncthreads();
+            __syncthreads();
+            lse_merge<WN, BM>(ea, M, m0, nt, reinterpret_cast<const float2*>(smem_w), tid, 64 * (NW + LW));
+        }
         return;
     }
 
@@ -626,6 +760,8 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_gemm_w(const uint16_t* __
     const int wm = wave / WN, wn = wave % WN;
     RopeOps<EPI == EPI_ROPE ? TM : 1> rope_ops;
     if constexpr (!SPLIT && EPI == EPI_ROPE) rope_load<TM, BN>(ea, M, m0 + wm * TM * 16, n0 + wn * TN * 16, lane, rope_ops);
+    int lse_lb[EPI == EPI_LSE ? TM : 1][4];
+    if constexpr (!SPLIT && EPI == EPI_LSE) lse_load<TM>(ea, M, N, m0 + wm * TM * 16, lane, lse_lb);
     f32x4 acc[NB][TM][TN];
 #pragma unroll
     for (int bb = 0; bb < NB; ++bb)
@@ -834,6 +970,12 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_gemm_w(const uint16_t* __
             }
     } else if constexpr (EPI == EPI_ROPE) {
         rope_apply<TM>(ea, M, m0 + wm * TM * 16, lane, rope_ops, acc[0]);
+    } else if constexpr (EPI == EPI_LSE) {
+        float2* sm = reinterpret_cast<float2*>(smem_w);
+        __syncthreads();  // compute and loader waves: the last tile's fragments are read, the ring's memory is free
+        lse_wave<TM, TN, BM>(ea, M, N, m0 + wm * TM * 16, n0 + wn * TN * 16, wm * TM * 16, wn, lane, sm, acc[0], lse_lb);
+        __syncthreads();
+        lse_merge<WN, BM>(ea, M, m0, nt, sm, tid, 64 * (NW + LW));
     } else {
         epi_tile<EPI, TM, TN>(ea, M, N, m0 + wm * TM * 16, n0 + wn * TN * 16, lane, acc[0], acc[NB - 1]);
     }
@@ -1360,7 +1502,7 @@ static void launch(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W,
                    const EpiArgs& ea, float* ws, int split, long up_off, bool partials) {
     using E = typename T::template For<EPI>;
     using S = typename T::template For<EPI_STORE>;
-    constexpr bool CAN_SPLIT = EPI != EPI_GEGLU && EPI != EPI_ROPE;
+    constexpr bool CAN_SPLIT = EPI != EPI_GEGLU && EPI != EPI_ROPE && EPI != EPI_LSE;
     constexpr auto kern = E::template kernel<false>();
     constexpr auto kern_split = S::template kernel<true>();
     const int nkt = (K + 63) / 64;
@@ -1442,6 +1584,48 @@ bool gemm_qkv_rope(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W,
         using T = decltype(t);
         if constexpr (T::ROPE) launch<T, EPI_ROPE>(s, A, lda, W, ldw, M, N, K, ea, nullptr, 1, 0, false);
         return T::ROPE;
+    });
+}
+
+// EPI_LSE is instantiated for the configurations choose() can return for a K = 2048, non-dual shape run unsplit:
+// the fallback's P64x64 / P128w (every vocabulary-wide N) and the table's W64x64, W128x128, Q256w, W288n.  Any
+// other configuration reaches here only when forced (pgmi_tune_gemm) and is refused.
+constexpr bool lse_has(int id) {
+    return id == P128w || id == P64x64 || id == Q256w || id == W288n || id == W64x64 || id == W128x128;
+}
+template <int ID, class T, class F>
+static bool lse_call(F&& f) {
+    if constexpr (lse_has(ID)) return f(T{});
+    else return false;
+}
+template <class F>
+static bool with_lse_cfg(int cfg, F&& f) {
+    switch (cfg) {
+#define X(id, name, fam, nw, wm, tm, tnw, st, lw, rl, rope) \
+    case id: return lse_call<id, Tile<fam, nw, wm, tm, tnw, st, lw, rl, rope>>(f);
+        PGMI_GEMM_CFGS(X)
+#undef X
+        default: return false;
+    }
+}
+
+int gemm_lse_tiles(int M, int N, int K) {
+    const Plan p = choose(M, N, K, false);
+    return with_lse_cfg(p.cfg, [](auto) { return true; }) ? (N + p.bn - 1) / p.bn : 0;
+}
+
+bool gemm_lse(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
+              const int64_t* labels, float2* part, float* lab) {
+    const Plan p = choose(M, N, K, false);
+    EpiArgs ea{};
+    ea.lse_labels = labels;
+    ea.lse_part = part;
+    ea.lse_lab = lab;
+    ea.lse_nt = (N + p.bn - 1) / p.bn;
+    return with_lse_cfg(p.cfg, [&](auto t) {
+        using T = decltype(t);
+        launch<T, EPI_LSE>(s, A, lda, W, ldw, M, N, K, ea, nullptr, 1, 0, false);
+        return true;
     });
 }
 

@@ -649,6 +649,68 @@ void argmax_rows(hipStream_t s, const float* x, int rows, int V, float* pmax, in
     if (nb > 1) hipLaunchKernelGGL(k_argmax_finish, dim3(rows), dim3(256), 0, s, pmax, pidx, nb, out, nullptr, 0, nullptr);
 }
 
+// ---------------------------------------------------------------- log-probabilities of rows of logits
+// log_softmax(x[row])[ids[row]] and logsumexp(x[row]) over fp32 rows (the loss of modeling_gemma.py:596-603 on
+// logits that already exist: the decode step's).  Split like argmax_rows: a (nb x rows) grid, each block leaves
+// its slice's (m, s = sum exp(x - m)) -- per thread in index order, then xor-shuffles, then the four waves in
+// order -- and one workgroup per row merges the nb pairs in ascending order in fp64.
+__global__ void __launch_bounds__(256) k_logprob_part(const float* __restrict__ x, int V, int slice,
+                                                      float* __restrict__ pm, float* __restrict__ ps) {
+    const int row = blockIdx.y, nb = gridDim.x, tid = threadIdx.x;
+    const float* xr = x + (long)row * V;
+    const int lo = blockIdx.x * slice, hi = min(V, lo + slice);
+    __shared__ float sv[4];
+    float mx = -INFINITY;
+    for (int i = lo + tid; i < hi; i += 256) mx = fmaxf(mx, xr[i]);
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if ((tid & 63) == 0) sv[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
+    __syncthreads();
+    const float ms = mx == -INFINITY ? 0.f : mx;
+    float s = 0.f;
+    for (int i = lo + tid; i < hi; i += 256) s += expf(xr[i] - ms);
+    for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+    if ((tid & 63) == 0) sv[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        pm[(long)row * nb + blockIdx.x] = mx;
+        ps[(long)row * nb + blockIdx.x] = ((sv[0] + sv[1]) + sv[2]) + sv[3];
+    }
+}
+
+__global__ void k_logprob_finish(const float* __restrict__ x, int V, const float* __restrict__ pm,
+                                 const float* __restrict__ ps, int nb, const int64_t* __restrict__ ids,
+                                 int64_t ignore_index, float* __restrict__ logprob, float* __restrict__ lse) {
+    const int row = blockIdx.x;
+    if (threadIdx.x != 0) return;
+    pm += (long)row * nb;
+    ps += (long)row * nb;
+    float mx = -INFINITY;
+    for (int i = 0; i < nb; ++i) mx = fmaxf(mx, pm[i]);
+    const double ms = mx == -INFINITY ? 0.0 : (double)mx;
+    double acc = 0.0;
+    for (int i = 0; i < nb; ++i) acc += (double)ps[i] * exp((double)pm[i] - ms);
+    const float l = (float)((double)mx + log(acc));
+    if (lse) lse[row] = l;
+    const int64_t id = ids[row];
+    float lp;
+    if (id == ignore_index) lp = 0.f;
+    else if (id < 0 || id >= V) lp = __builtin_nanf("");
+    else lp = x[(long)row * V + id] - l;
+    logprob[row] = lp;
+}
+
+void logprob_rows(hipStream_t s, const float* x, int rows, int V, const int64_t* ids, int64_t ignore_index, float* pm,
+                  float* ps, float* logprob, float* lse) {
+    // rows * nb <= argmax_scratch_parts(): the caller passes at most that many rows per call
+    int nb = std::max(1, std::min(argmax_scratch_parts() / rows, std::min(128, (V + 2047) / 2048)));
+    const int slice = (V + nb - 1) / nb;
+    nb = (V + slice - 1) / slice;
+    hipLaunchKernelGGL(k_logprob_part, dim3(nb, rows), dim3(256), 0, s, x, V, slice, pm, ps);
+    hipLaunchKernelGGL(k_logprob_finish, dim3(rows), dim3(64), 0, s, x, V, pm, ps, nb, ids, ignore_index, logprob, lse);
+}
+
 // ---------------------------------------------------------------- synthetic weights (bench / tests)
 // Same recipe as oracle/wgen.c: u = splitmix64(key + i), v = ((u>>40) - 2^23) * 2^-23,
 // w = bf16(offset + v*scale) with the two f32 roundings kept separate.

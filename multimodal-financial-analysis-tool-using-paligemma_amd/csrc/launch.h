@@ -17,6 +17,8 @@ enum Epi : int {
     EPI_GEGLU = 7,      // out = bf16(bf16(gelu(bf16(acc_gate))) * bf16(acc_up))  (dual B)
     EPI_ROPE = 8,       // Gemma q|k|v rows: RoPE on q and k, q -> q_out, k / v appended to the KV cache
                         // (modeling_gemma.py:197-198,259); gemm_qkv_rope only
+    EPI_LSE = 9,        // no output matrix: per (row, column tile) the pair (max, sum exp(x - max)) of x = bf16(acc),
+                        // and x at the row's label column (modeling_gemma.py:596-603); gemm_lse only
 };
 
 struct EpiArgs {
@@ -42,6 +44,12 @@ struct EpiArgs {
     int L = 1;
     int nh = 0;
     int nkv = 0;
+    // EPI_LSE: row m's label column lse_labels[m] (any value; one outside [0, N) selects nothing), the pair of
+    // column tile nt -> lse_part[m * lse_nt + nt], the label's logit -> lse_lab[m]
+    const int64_t* lse_labels = nullptr;
+    float2* lse_part = nullptr;
+    float* lse_lab = nullptr;
+    int lse_nt = 0;
 };
 
 // C[M,N] = A[M,K] (row-major, lda) x W[N,K]^T (row-major, ldw).  For EPI_GEGLU the
@@ -57,6 +65,17 @@ bool gemm_qkv_rope(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W,
 int gemm(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
          Epi epi, const EpiArgs& ea, float* ws, size_t ws_bytes, int up_offset_rows = 0, bool defer = false);
 size_t gemm_ws_bytes(int M, int N, int K);
+// The lm_head GEMM without its output (EPI_LSE): the plan gemm() takes for the shape, never split, so each logit is
+// bit for bit the one gemm(EPI_F32) writes.  part: [M][gemm_lse_tiles(M, N, K)] pairs, lab: [M].  gemm_lse_tiles
+// returns 0 when the shape's (or the forced) tile configuration has no EPI_LSE instance; gemm_lse then launches
+// nothing and returns false.  lse_combine merges each row's pairs in ascending tile order (fp64) into lse[row]
+// (may be null) and logprob[row] = lab[row] - lse[row]: 0 for labels[row] == ignore_index, NaN for any other
+// label outside [0, N).
+int gemm_lse_tiles(int M, int N, int K);
+bool gemm_lse(hipStream_t s, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
+              const int64_t* labels, float2* part, float* lab);
+void lse_combine(hipStream_t s, const float2* part, int n_nt, const float* lab, const int64_t* labels, int rows, int N,
+                 int64_t ignore_index, float* logprob, float* lse);
 void gemm_force_plan(int cfg, int split);  // cfg < 0: automatic
 int gemm_force_shape(int M, int N, int K, int dual, int cfg, int split);  // cfg < 0: remove the override
 // probe: the next GEMM kernel launched takes these events as its own start / stop (hipExtLaunchKernelGGL)
@@ -135,6 +154,11 @@ void argmax_finish(hipStream_t s, int B, const float* pmax, const int* pidx, int
                    StepState* adv = nullptr, int64_t* hist = nullptr, int adv_n = 1);
 int argmax_scratch_parts();
 void argmax_rows(hipStream_t s, const float* x, int rows, int V, float* pmax, int* pidx, int64_t* out);
+// lse[row] (may be null) = logsumexp(x[row]) and logprob[row] = x[row][ids[row]] - lse[row] over fp32 rows
+// [rows][V] (0 for ids[row] == ignore_index, NaN for any other id outside [0, V)); pm / ps: scratch of
+// argmax_scratch_parts() floats each
+void logprob_rows(hipStream_t s, const float* x, int rows, int V, const int64_t* ids, int64_t ignore_index, float* pm,
+                  float* ps, float* logprob, float* lse);
 void eos_update(hipStream_t s, int64_t* next, int* finished, int B, int64_t eos, int64_t pad, int* n_alive);
 
 // ---------------------------------------------------------------- attention

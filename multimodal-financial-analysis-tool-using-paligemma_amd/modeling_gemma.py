@@ -486,6 +486,10 @@ class PaliGemmaForConditionalGeneration(nn.Module):
     # KV-cached decode steps run the greedy continuation one step ahead of the caller (pgmi/lookahead.py):
     # bit-identical results, the host's per-token work overlaps the next step; off after two misses per cache
     pgmi_lookahead: bool = True
+    # forward(labels=...): take the loss from the final-normed rows of a lazy prefill result through
+    # Engine.lm_logprobs -- only the rows whose shifted label is live are multiplied, and the logits stay
+    # un-materialised.  Off: torch's CrossEntropyLoss on the materialised (B, L, V) tensor, as the reference
+    pgmi_fused_loss: bool = False
 
     def __init__(self, config: PaliGemmaConfig):
         super().__init__()
@@ -631,7 +635,7 @@ class PaliGemmaForConditionalGeneration(nn.Module):
             else:
                 logits = _run_lm(eng, kv_cache, B, L, pos, embeds=merged, logits_rows=rows)
                 if mode == "lazy":
-                    logits = LazyLogits(logits, eng.final_hidden(B * L), eng.lm_head, B, L)
+                    logits = LazyLogits(logits, eng.final_hidden(B * L), eng.lm_head, B, L, eng.shifted_logprobs)
         elif cache_len == 0 or kv_cache is None:
             # prefill (modeling_gemma.py:532-535: positions 0..L-1), merge on the device
             img = eng.project(eng.vision(pixel_values)) if pixel_values is not None else None
@@ -639,7 +643,7 @@ class PaliGemmaForConditionalGeneration(nn.Module):
             logits = _run_lm(eng, kv_cache, B, L, pos, ids=input_ids, image_feats=img, logits_rows=rows,
                              before_commit=chk.wait)
             if mode == "lazy":
-                logits = LazyLogits(logits, eng.final_hidden(B * L), eng.lm_head, B, L)
+                logits = LazyLogits(logits, eng.final_hidden(B * L), eng.lm_head, B, L, eng.shifted_logprobs)
         else:
             # KV-cached decode step; pixel_values of inference.py's loop would only produce image
             # features that the merge discards (the new token is not <image>), so they are skipped
@@ -664,7 +668,10 @@ class PaliGemmaForConditionalGeneration(nn.Module):
     def _pack(self, logits, labels, kv_cache, return_dict):
         """The loss and return conventions of modeling_gemma.py:598-617."""
         loss = None
-        if labels is not None:
+        if labels is not None and self.pgmi_fused_loss and isinstance(logits, LazyLogits) and \
+                not logits.is_materialized:
+            loss = logits.shifted_loss(labels, self.config.ignore_index)
+        elif labels is not None:
             shift_logits = logits[..., :-1, :].contiguous()
             shift_labels = labels[..., 1:].contiguous().to(logits.device)
             loss = CrossEntropyLoss(ignore_index=self.config.ignore_index)(

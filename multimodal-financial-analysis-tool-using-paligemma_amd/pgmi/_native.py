@@ -82,6 +82,9 @@ SIGNATURES = {
     "pgmi_argmax": (i32, [vp, vp, i32, i32, vp, vp]),
     "pgmi_lm_head": (i32, [vp, vp, i32, vp, vp]),
     "pgmi_lm_final_hidden": (i32, [vp, vp, i32, vp]),
+    "pgmi_lm_logprobs": (i32, [vp, vp, i32, vp, i64, vp, vp, vp]),
+    "pgmi_logprobs": (i32, [vp, vp, i32, i32, vp, i64, vp, vp, vp]),
+    "pgmi_op_lm_logprobs": (i32, [vp, vp, vp, i32, i32, i32, vp, i64, vp, vp, vp]),
     "pgmi_comm_unique_id": (i32, [vp]),
     "pgmi_comm_init": (i32, [i32, i32, i32, vp, ctypes.POINTER(vp)]),
     "pgmi_comm_destroy": (i32, [vp]),

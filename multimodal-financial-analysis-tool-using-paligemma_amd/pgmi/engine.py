@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -42,6 +42,15 @@ def config_dict(cfg) -> dict:
         "pad_token_id": -1 if pad is None else int(pad),
         "hidden_size": get("hidden_size", 2048),
     }
+
+
+class Score(NamedTuple):
+    """Engine.score's result: per-token log-probabilities (0 where ignored), each row's sum and live-token count,
+    and the reference's loss (modeling_gemma.py:596-603)."""
+    logprobs: torch.Tensor
+    sums: torch.Tensor
+    counts: torch.Tensor
+    loss: torch.Tensor
 
 
 class Engine:
@@ -311,6 +320,89 @@ class Engine:
         N.check(self.lib.pgmi_lm_head(self.ctx, x.data_ptr(), x.shape[0], out.data_ptr(), self._s()), "pgmi_lm_head")
         return out
 
+    def lm_logprobs(self, normed: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100,
+                    return_lse: bool = False):
+        """Token log-probabilities of the reference's loss (modeling_gemma.py:596-603) over final-normed rows
+        without the logits (pgmi_lm_logprobs): normed (..., hidden) bf16, labels (...) int64, already shifted.
+        Returns fp32 (rows,): log_softmax(lm_head(normed))[label], 0 where the label is ignore_index, NaN for any
+        other label outside the vocabulary; with return_lse also logsumexp per row."""
+        self._ready()
+        x = normed.to(self.device, torch.bfloat16).reshape(-1, normed.shape[-1]).contiguous()
+        lb = labels.to(self.device, torch.int64).reshape(-1).contiguous()
+        if lb.numel() != x.shape[0]:
+            raise ValueError(f"need one label per row: {lb.numel()} != {x.shape[0]}")
+        out = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
+        lse = torch.empty_like(out) if return_lse else None
+        N.check(self.lib.pgmi_lm_logprobs(self.ctx, x.data_ptr(), x.shape[0], lb.data_ptr(), int(ignore_index),
+                                          out.data_ptr(), N.ptr(lse), self._s()), "pgmi_lm_logprobs")
+        return (out, lse) if return_lse else out
+
+    def logprobs(self, logits: torch.Tensor, ids: torch.Tensor, ignore_index: int = -100, return_lse: bool = False):
+        """log_softmax(logits)[id] per row of existing fp32 logits (..., V) (pgmi_logprobs; the rule of
+        modeling_gemma.py:596-603): 0 where the id is ignore_index, NaN for any other id outside [0, V)."""
+        x = logits.reshape(-1, logits.shape[-1]).to(self.device, torch.float32).contiguous()
+        lb = ids.to(self.device, torch.int64).reshape(-1).contiguous()
+        if lb.numel() != x.shape[0]:
+            raise ValueError(f"need one id per row: {lb.numel()} != {x.shape[0]}")
+        out = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
+        lse = torch.empty_like(out) if return_lse else None
+        N.check(self.lib.pgmi_logprobs(self.ctx, x.data_ptr(), x.shape[0], x.shape[1], lb.data_ptr(), int(ignore_index),
+                                       out.data_ptr(), N.ptr(lse), self._s()), "pgmi_logprobs")
+        return (out, lse) if return_lse else out
+
+    @torch.no_grad()
+    def shifted_logprobs(self, hidden: torch.Tensor, shift_labels: torch.Tensor, live: Optional[torch.Tensor] = None,
+                         ignore_index: int = -100):
+        """The one place the shifted loss is taken from hidden rows (modeling_gemma.py:596-603): hidden (B * L,
+        hidden) final-normed rows, shift_labels (B, L - 1) = labels[:, 1:], live (B, L - 1) bool (default: the
+        labels that are not ignore_index).  Only the live rows go through the lm_head (one index_select, one host
+        sync for their indices).  Returns (logprobs (B, L - 1) fp32 with 0 where not live, live, loss): loss =
+        -mean over the live tokens in fp64, NaN when there is none."""
+        shift = shift_labels.to(self.device, torch.int64)
+        B, L1 = shift.shape
+        L = L1 + 1
+        if live is None:
+            live = shift != ignore_index
+        out = torch.zeros((B, L1), dtype=torch.float32, device=self.device)
+        at = live.nonzero()  # the host sync
+        if at.shape[0] == 0:
+            return out, live, torch.full((), float("nan"), dtype=torch.float32, device=self.device)
+        out[at[:, 0], at[:, 1]] = self.lm_logprobs(hidden.index_select(0, at[:, 0] * L + at[:, 1]),
+                                                   shift[at[:, 0], at[:, 1]], ignore_index)
+        return out, live, (-out.sum(dtype=torch.float64) / at.shape[0]).float()
+
+    @torch.no_grad()
+    def score(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], labels: torch.Tensor,
+              attention_mask: Optional[torch.Tensor] = None, ignore_index: int = -100) -> "Score":
+        """The reference's forward(labels=...) loss (modeling_gemma.py:596-603) per token, from one prefill:
+        position j is scored against labels[:, j + 1], and only the rows whose shifted label is live go through
+        the lm_head (one index_select on the final-normed rows, one host sync; no (B, L, V) tensor exists).
+
+        attention_mask (B, L) of 0 / 1: a ragged batch as Engine.generate takes it; ids and labels are moved to
+        the right-padded form and pad positions count as ignored whatever their label.  pixel_values None: a
+        text-only prompt.  Returns Score(logprobs (B, L - 1) fp32 with 0 where ignored, sums (B,), counts (B,),
+        loss = -mean over the live tokens, NaN when there is none)."""
+        ids = input_ids.to(self.device, torch.int64)
+        lab = labels.to(self.device, torch.int64)
+        if tuple(lab.shape) != tuple(ids.shape):
+            raise ValueError(f"labels {tuple(lab.shape)} do not match input_ids {tuple(ids.shape)}")
+        lens = R.lengths_from_mask(attention_mask) if attention_mask is not None else None
+        if lens is not None:
+            ids, lens = R.right_pad(ids, attention_mask)
+            lab, _ = R.right_pad(lab, attention_mask, pad_id=ignore_index)
+        ids = ids.contiguous()
+        B, L = ids.shape
+        feats = self.project(self.vision(pixel_values)) if pixel_values is not None else None
+        kv = self.scratch_kv(B, L)
+        self.lm_forward(kv, 0, torch.arange(L).expand(B, L), ids=ids, image_feats=feats, logits_rows=1, lens=lens)
+        hidden = self.final_hidden(B * L)
+        shift = lab[:, 1:]
+        live = shift != ignore_index
+        if lens is not None:  # the scored token j + 1 must be a real one
+            live &= (torch.arange(1, L, device=self.device)[None, :] < lens.to(self.device)[:, None])
+        out, live, loss = self.shifted_logprobs(hidden, shift, live, ignore_index)
+        return Score(out, out.sum(1), live.sum(1), loss)
+
     def decode(self, ids: torch.Tensor, kv: torch.Tensor, kv_len: int, position: int, logits: torch.Tensor = None,
                next_ids: torch.Tensor = None, graph: bool = False) -> torch.Tensor:
         """One KV-cached decode step for B sequences; returns logits (B, V) fp32."""
@@ -467,7 +559,7 @@ class Engine:
                  kv: torch.Tensor = None, do_sample: bool = False, temperature: float = 0.8, top_p: float = 0.9,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, sync_every: int = 16, return_lengths: bool = False,
-                 attention_mask: Optional[torch.Tensor] = None):
+                 attention_mask: Optional[torch.Tensor] = None, return_logprobs: bool = False):
         """Batched generation: prefill, then n_tokens-1 decode steps
         with the next token picked on the device -- greedy argmax, or with do_sample the
         temperature + top-p draw of inference.py:64-66 -- and no host sync per token.
@@ -485,7 +577,12 @@ class Engine:
         (padding="longest", left or right).  Each row then runs with its own length -- prefill over its
         real tokens, decode at its own KV row and rotary position (pgmi_lm_forward_ragged /
         pgmi_decode_ragged) -- and generates what it would alone.  No mask, or all ones: the lock-step
-        path.  kv defaults to new_kv(B, L + n_tokens + 1) either way."""
+        path.  kv defaults to new_kv(B, L + n_tokens + 1) either way.
+
+        return_logprobs: also return fp32 (B, n_tokens) (last in the returned tuple): the log-probability of each
+        emitted token under softmax of the raw step logits (pgmi_logprobs) -- no temperature and no top-p
+        renormalisation, whatever the sampling settings -- and 0 for the pad emitted after a row's eos.  The
+        loop then runs one launch per step, as do_sample does; the tokens are the same."""
         ids = input_ids.to(self.device, torch.int64)
         lens = R.lengths_from_mask(attention_mask) if attention_mask is not None else None
         if lens is not None:
@@ -503,6 +600,9 @@ class Engine:
             toks[:, 0] = self.sample_top_p(logits[:, 0], top_p, temperature, u=us[0])
         else:
             toks[:, 0] = self.argmax(logits[:, 0])
+        if return_logprobs:
+            lps = torch.zeros((B, n_tokens), dtype=torch.float32, device=self.device)
+            lps[:, 0] = self.logprobs(logits[:, 0], toks[:, 0])
         # per-B persistent buffers (step logits, fed-back ids, sampled step's argmax, chunk record): stable
         # pointers, so repeated generate calls on the same cache replay the decode graphs they captured
         bufs = self._gen_buf.get(B)
@@ -536,7 +636,7 @@ class Engine:
             self._eos_update(cur, finished, int(eos_token_id), pad, alive)
             toks[:, 0] = cur
         n_done = n_tokens
-        if not do_sample and not stop and graph and n_tokens > 1 and B >= self.GEN_MIN_BATCH:
+        if not do_sample and not stop and not return_logprobs and graph and n_tokens > 1 and B >= self.GEN_MIN_BATCH:
             # greedy without a stop token: GEN_CHUNK steps per hipGraph launch (pgmi_decode_steps / _ragged), the
             # argmax fed back in place and every step's token kept in a device record
             t = 1
@@ -555,16 +655,24 @@ class Engine:
                     cur.copy_(self.sample_top_p(step_logits, top_p, temperature, u=us[t]))
                 else:  # greedy: the argmax is fed back in place (next_ids == ids)
                     step(t, cur)
+                if return_logprobs:  # of the token the step picked; rows that stopped earlier emit pad: 0
+                    lp = self.logprobs(step_logits, cur)
+                    lps[:, t] = lp.masked_fill_(finished != 0, 0.0) if stop else lp
                 if stop:
                     self._eos_update(cur, finished, int(eos_token_id), pad, alive)
                 toks[:, t] = cur
         if not stop:
-            return (toks, torch.full((B,), n_tokens, dtype=torch.int64, device=self.device)) if return_lengths else toks
-        toks = toks[:, :n_done]
-        hit = toks == int(eos_token_id)
-        first = torch.where(hit.any(1), hit.int().argmax(1) + 1, torch.full_like(hit[:, 0], n_done, dtype=torch.int64))
-        toks = toks[:, :int(first.max().item())].contiguous()
-        return (toks, first.to(torch.int64)) if return_lengths else toks
+            ret = (toks, torch.full((B,), n_tokens, dtype=torch.int64, device=self.device)) if return_lengths else (toks,)
+        else:
+            toks = toks[:, :n_done]
+            hit = toks == int(eos_token_id)
+            first = torch.where(hit.any(1), hit.int().argmax(1) + 1,
+                                torch.full_like(hit[:, 0], n_done, dtype=torch.int64))
+            toks = toks[:, :int(first.max().item())].contiguous()
+            ret = (toks, first.to(torch.int64)) if return_lengths else (toks,)
+        if return_logprobs:
+            ret = ret + (lps[:, :toks.shape[1]].contiguous(),)
+        return ret if len(ret) > 1 else ret[0]
 
     def _eos_update(self, next_ids: torch.Tensor, finished: torch.Tensor, eos: int, pad: int,
                     n_alive: Optional[torch.Tensor]) -> None:

@@ -24,10 +24,11 @@ import torch
 
 
 class LazyLogits:
-    def __init__(self, last: torch.Tensor, hidden: torch.Tensor, lm_head, B: int, L: int):
+    def __init__(self, last: torch.Tensor, hidden: torch.Tensor, lm_head, B: int, L: int, shifted_logprobs=None):
         """last: (B, 1, V) fp32 logits of position L-1; hidden: (B*L, H) final-normed rows;
-        lm_head: rows -> (rows, V) fp32 (Engine.lm_head)."""
-        self._last, self._hidden, self._lm_head = last, hidden, lm_head
+        lm_head: rows -> (rows, V) fp32 (Engine.lm_head); shifted_logprobs: Engine.shifted_logprobs, for
+        shifted_loss."""
+        self._last, self._hidden, self._lm_head, self._shifted_logprobs = last, hidden, lm_head, shifted_logprobs
         self._B, self._L, self._V = B, L, last.shape[-1]
         self._full = None
 
@@ -76,6 +77,15 @@ class LazyLogits:
             self._last = full[:, -1:, :]
             self._hidden = None
         return self._full
+
+    def shifted_loss(self, labels: torch.Tensor, ignore_index: int) -> torch.Tensor:
+        """The reference's loss (modeling_gemma.py:596-603: position j against labels[:, j + 1], mean over the
+        labels that are not ignore_index, NaN when there is none) from the hidden rows, without materialising:
+        only the live rows go through the lm_head (Engine.shifted_logprobs, which Engine.score also uses)."""
+        if self._hidden is None or self._shifted_logprobs is None:
+            raise RuntimeError("shifted_loss needs the un-materialised hidden rows and Engine.shifted_logprobs")
+        shift = labels[..., 1:].reshape(self._B, self._L - 1)
+        return self._shifted_logprobs(self._hidden, shift, None, ignore_index)[2]
 
     def _last_row_index(self, idx):
         """idx selecting within the last position only -> the equivalent index into (B, 1, V)."""
