@@ -208,6 +208,45 @@ int pgmi_graph_count(const pgmi_ctx* ctx, int which);
  * -1 = back to the default.  Same arithmetic either way (bf16 normalised rows);
  * drops captured decode graphs.  A tuning / test switch, no reference counterpart. */
 int pgmi_set_decode_staged_norm(pgmi_ctx* ctx, int on);
+/* Decode at batch 1-2: lossless 13-bit weight images.  The step's three streaming projections -- gate|up, down
+ * and lm_head, 95 % of its bytes -- can read a 13-bit image of their weights instead of the bf16 rows: the
+ * sign-and-mantissa byte of every weight plus a 5-bit code of its exponent relative to the tensor's largest
+ * (csrc/pack13.h).  The kernels rebuild each bf16 value bit for bit before the same dot products,
+ * so every output is identical to the bf16 kernels'; the step streams 13/16 of the bytes.
+ *   - Candidate tensors: every layer's gate|up (one tensor) and down, and the tied embedding as lm_head reads it:
+ *     2 x layers + 1.  A tensor is packed only if it FITS: no element's exponent field lies in [1, e_hi - 31], e_hi
+ *     being the tensor's largest (zeros and denormals, field 0, have a code of their own).  A tensor that does not
+ *     fit keeps the bf16 kernel as a whole.
+ *   - The images are built on the stream of the first decode step with B <= 2 after a pgmi_prepare (one stream
+ *     synchronisation; never inside a caller's capture) and rebuilt after the next pgmi_prepare, which every
+ *     weight update must be followed by.  They cost 13/16 of the candidates' bf16 bytes in device memory beside
+ *     the bf16 weights, which stay resident for the prefill and the embedding look-up: 3.80 GB at the 3B shapes.
+ *     If a kind's buffer cannot be allocated, that kind keeps the bf16 kernels.
+ *   - pgmi_set_decode_packed: on = 0 reads the bf16 rows everywhere; on = 1..7 is a mask of the kinds read packed
+ *     (1 gate|up, 2 down, 4 lm_head), at B = 1 and B = 2 alike; on < 0 restores the default: the kinds whose
+ *     kernel measured faster packed, all three at B = 1 and lm_head alone at B = 2 (two rows double the dot
+ *     products per decoded weight: gate|up and down become VALU-limited there).  A change drops the captured decode
+ *     graphs of B <= 2 and the prefill graphs (the last-row-only prefill's projections follow the setting); the
+ *     batched path (B >= 3) is not touched.  Text hidden 2048 / intermediate 16384 only; other shapes stay raw.
+ *   - pgmi_decode_packed_info: info[0] the mask in force at B = 1 ([8]: at B = 2), [1] candidate tensors the
+ *     B = 1 step reads packed now, [2] reads raw,
+ *     [3] bytes of the packed ones' images, [4] bf16 bytes of the raw ones, [5] 1 if an image allocation failed
+ *     since the last pgmi_prepare, [6] 1 if the allocation of the batched (B >= 3) decode's fragment-major images
+ *     failed (that path then reads the row-major weights: same results, slower), [7] mask of the kinds scanned
+ *     since the last pgmi_prepare.  n >= PGMI_PACKED_INFO_N.
+ *   - pgmi_decode_packed_tensor: 1 if the B = 1 step reads the tensor of `kind` (and `layer`; ignored for lm_head)
+ *     packed now, 0 if raw. */
+#define PGMI_PACKED_INFO_N 9
+int pgmi_set_decode_packed(pgmi_ctx* ctx, int on);
+int pgmi_decode_packed_info(const pgmi_ctx* ctx, int64_t* info, int n);
+int pgmi_decode_packed_tensor(const pgmi_ctx* ctx, int kind, int layer);
+/* The 13-bit format on the host (tests; no device): pgmi_pack13_scan gives e_hi and whether n bf16 values fit;
+ * pgmi_pack13_bytes the image size of rows x K values (K a multiple of 2048; -1 otherwise); _encode / _decode
+ * write the image and rebuild the bf16 values through the functions the kernels use. */
+int pgmi_pack13_scan(const uint16_t* w, int64_t n, int* e_hi, int* fits);
+int64_t pgmi_pack13_bytes(int64_t rows, int64_t K);
+int pgmi_pack13_encode(const uint16_t* w, int64_t rows, int64_t K, int e_hi, uint8_t* image);
+int pgmi_pack13_decode(const uint8_t* image, int64_t rows, int64_t K, int e_hi, uint16_t* w);
 /* lm_head + .float() of GemmaForCausalLM (modeling_gemma.py:417-418) over final-normed hidden
  * rows: logits (device fp32 [rows][vocab]) = fp32(bf16(normed . E^T)) with the tied embedding E.
  * Together with pgmi_lm_final_hidden this materialises the prefill's all-row logits on demand
@@ -261,6 +300,11 @@ int pgmi_eos_update(pgmi_ctx* ctx, int64_t* next_ids, int32_t* finished, int B, 
  * dominant kernel in isolation): 1 o_proj+residual, 2 RMSNorm+gate/up+GeGLU, 3 down+residual,
  * 4 final norm + lm_head (+argmax partials; layer ignored). */
 int pgmi_decode_kernel(pgmi_ctx* ctx, int which, int layer, int B, void* stream);
+/* Test hook: copy `bytes` bytes between the decode workspace pgmi_decode_kernel works on and the caller's device
+ * memory `buf` (write != 0: buf -> workspace): which 0 = h (bf16 [max_batch][hidden], kernel 2's input, kernel 1's
+ * and 3's in/out), 1 = act (bf16 [max_batch][intermediate], kernel 2's output, 3's input), 2 = kernel 4's logits
+ * (fp32 [max_batch][vocab]).  Stream-ordered.  PGMI_E_ARG: a byte count outside the buffer. */
+int pgmi_debug_decode_buffer(pgmi_ctx* ctx, int which, void* buf, int64_t bytes, int write, void* stream);
 
 /* Image preprocessing on the GPU (processing_paligemma.py:13-49, process_images): PIL-exact
  * BICUBIC resize of one decoded RGB image (uint8 HWC, device memory, H x W) to out_h x out_w,

@@ -22,6 +22,7 @@
 #include "../../include/pgmi.h"
 #include "common.h"
 #include "launch.h"
+#include "pack13.h"
 #include "safetensors_hdr.h"
 
 using namespace pgmi;
@@ -87,12 +88,21 @@ struct TextLayerW {
     const uint16_t *qkv, *o, *gate_up, *down, *in_norm, *post_norm;
     // batched decode (B >= 3): this layer's fragment-major images (ensure_mf_image), null while the image is absent
     const uint16_t *mf_gate_up = nullptr, *mf_qkv = nullptr, *mf_o = nullptr, *mf_down = nullptr;
+    // decode at B <= 2: the 13-bit images of gate|up and down (ensure_pk_image), img null while absent or raw
+    PkW pk_gate_up, pk_down;
 };
 struct WeightTable {
     const uint16_t *patch_conv_w, *patch_b, *pos_emb, *post_ln_w, *post_ln_b, *proj_w, *proj_b, *embed, *final_norm;
     std::vector<VisionLayerW> v;
     std::vector<TextLayerW> t;
+    PkW pk_embed;  // the tied embedding's 13-bit image as lm_head reads it (the raw rows stay for look-up and prefill)
 };
+
+// weight kinds with a 13-bit image (bits of pgmi_set_decode_packed's mask)
+enum { PK_GATE_UP = 1, PK_DOWN = 2, PK_LM_HEAD = 4, PK_ALL = 7 };
+// the default: the kinds whose kernel measured faster packed, per batch (at B = 2 gate|up and
+// down are VALU-limited and lose 4 %, lm_head still gains 8 %)
+constexpr int kPkDefaultB1 = PK_ALL, kPkDefaultB2 = PK_LM_HEAD;
 
 struct pgmi_ctx {
     pgmi_config c;
@@ -129,6 +139,15 @@ struct pgmi_ctx {
     // order), o_proj and down weights (mf_swizzle); laid out by ensure_mf_image, read through w.t[i].mf_*
     uint16_t* mfw = nullptr;
     bool mfw_dirty = false;  // the fragment-major images are (re)built by the next batched decode step
+    bool mfw_alloc_failed = false;  // their allocation failed: the batched decode reads the row-major weights
+    // decode at B <= 2: 13-bit images (pack13.h) of every layer's gate|up and down rows and of the tied embedding,
+    // one buffer per kind (PK_GATE_UP, PK_DOWN, PK_LM_HEAD); built by ensure_pk_image, read through w.t[i].pk_* /
+    // w.pk_embed.  pk_mask: the kinds the step reads packed (pgmi_set_decode_packed; < 0: the per-batch default,
+    // pk_mask_for); pk_done: the kinds scanned (and packed, where they fit) or given up since the last pgmi_prepare
+    uint8_t* pk_buf[3] = {nullptr, nullptr, nullptr};
+    unsigned* pk_stat = nullptr;
+    int pk_mask = -1, pk_done = 0;
+    bool pk_alloc_failed = false;
     float *opart, *pmax, *dlogits, *amax_v;
     int *pidx, *amax_i;
     int max_chunks;
@@ -164,6 +183,26 @@ struct pgmi_ctx {
 };
 
 namespace {
+
+// the kinds a B-row step reads packed: the caller's mask, or the measured default of that batch size
+int pk_mask_for(const pgmi_ctx* x, int B) {
+    return x->pk_mask >= 0 ? x->pk_mask : B <= 1 ? kPkDefaultB1 : kPkDefaultB2;
+}
+
+// the image a B-row streaming GEMV of `kind` reads now: w, or none (the bf16 rows) while the kind is switched
+// off, not built since the last pgmi_prepare, or the tensor did not fit (w.img null)
+PkW pk_use(const pgmi_ctx* x, int B, int kind, const PkW& w) {
+    const bool on = B <= 2 && B < gemv_mf_min_batch() && (pk_mask_for(x, B) & x->pk_done & kind);
+    return on ? w : PkW{};
+}
+
+// the weights changed (pgmi_prepare, a new slab): no image is valid until ensure_pk_image has rebuilt it
+void pk_forget(pgmi_ctx* x) {
+    x->pk_done = 0;
+    x->pk_alloc_failed = false;
+    x->w.pk_embed = PkW{};
+    for (auto& t : x->w.t) t.pk_gate_up = t.pk_down = PkW{};
+}
 
 int n_img(const pgmi_config& c) { return (c.v_image / c.v_patch) * (c.v_image / c.v_patch); }
 
@@ -489,6 +528,7 @@ int pgmi_bind_weights(pgmi_ctx* x, void* slab) {
     if (!x || !slab) return fail(PGMI_E_ARG, "null argument");
     if (reinterpret_cast<uintptr_t>(slab) % 256 != 0) return fail(PGMI_E_ARG, "weight slab must be 256-byte aligned");
     x->slab = reinterpret_cast<uint8_t*>(slab);
+    pk_forget(x);
     x->dgraphs.clear();
     x->pgraphs.clear();
     return bind_tables(x);
@@ -735,6 +775,8 @@ int pgmi_prepare(pgmi_ctx* x) {
     // call (ensure_mf_image), not here -- a context that never decodes a batch (the drop-in's single-sequence
     // loop on its max_batch-8 context) neither allocates their 3.96 GB nor pays for the swizzle
     x->mfw_dirty = c.max_batch >= gemv_mf_min_batch() && c.t_intermediate % 32 == 0 && c.t_hidden % 32 == 0;
+    // the 13-bit images of the B <= 2 step likewise: rebuilt from the new weights by the next such step
+    pk_forget(x);
     std::vector<uint16_t> cs, sn;
     if (!x->host_cos.empty()) {
         cs = x->host_cos;
@@ -1038,8 +1080,9 @@ static int lm_rows(pgmi_ctx* x, hipStream_t s, int b0, int B, int L, void* kv, i
                 attention_prefill(s, 256, a);
                 gemv_res(s, B, NH * HD, x->dAO, w.o, H, lastrows, x->ws);
             }
-            gemv_geglu(s, B, lastrows, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT);
-            gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, lastrows, x->ws);
+            gemv_geglu(s, B, lastrows, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
+                       pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
+            gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, lastrows, x->ws, pk_use(x, B, PK_DOWN, w.pk_down));
             break;
         }
         attention_prefill(s, 256, a);
@@ -1072,7 +1115,8 @@ static int lm_rows(pgmi_ctx* x, hipStream_t s, int b0, int B, int L, void* kv, i
             HIPCHK(hipMemcpy2DAsync(lastrows, (size_t)H * 2, Hs + (size_t)(L - 1) * H, (size_t)L * H * 2,
                                     (size_t)H * 2, B, hipMemcpyDeviceToDevice, s));
         int nparts = 0;
-        gemv_logits(s, B, lastrows, fnorm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts);
+        gemv_logits(s, B, lastrows, fnorm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts, nullptr, nullptr,
+                    nullptr, nullptr, 1, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed));
     }
     LAUNCHCHK();
     return 0;
@@ -1144,15 +1188,16 @@ static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, vo
                           i + 1 < c.t_layers ? x->w.t[i + 1].in_norm : nullptr, eps, x->dHn, w.mf_down);
             continue;
         }
-        gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT);
-        gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws);
+        gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
+                   pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
+        gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws, pk_use(x, B, PK_DOWN, w.pk_down));
     }
     int nparts = 0;
     int64_t* nx = next_ids ? next_ids : x->d_next;
     // the step's last work also advances the device step state (pgmi_decode skips its host-side
     // set when the next call continues the sequence): lm_head's last workgroup, or argmax_finish
     if (!gemv_logits(s, B, x->dH, x->w.final_norm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts, x->lm_done, nx,
-                     st, hist, adv_n))
+                     st, hist, adv_n, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed)))
         argmax_finish(s, B, x->pmax, x->pidx, nparts, nx, st, hist, adv_n);
     return launcher_error();  // (inside a capture too: a step with a launch missing is never instantiated)
 }
@@ -1228,8 +1273,10 @@ static int ensure_mf_image(pgmi_ctx* x, hipStream_t s) {
         void* p = nullptr;
         if (hipMalloc(&p, per * c.t_layers * sizeof(uint16_t)) != hipSuccess) {
             (void)hipGetLastError();  // out of memory: keep the row-major form
+            x->mfw_alloc_failed = true;  // (reported by pgmi_decode_packed_info)
             return 0;
         }
+        x->mfw_alloc_failed = false;
         x->allocs.push_back(p);
         x->mfw = reinterpret_cast<uint16_t*>(p);
         x->dgraphs.clear();  // steps captured before held the row-major launches
@@ -1245,6 +1292,199 @@ static int ensure_mf_image(pgmi_ctx* x, hipStream_t s) {
         w.mf_gate_up = gu; w.mf_qkv = qkv; w.mf_o = o; w.mf_down = down;
     }
     LAUNCHCHK();
+    return 0;
+}
+
+// captured decode steps of B <= 2 rows (key[0] = B, decode_step): they hold the launches of the other weight form
+static void drop_small_batch_graphs(GraphCache& g) {
+    for (auto it = g.map.begin(); it != g.map.end();) {
+        if (!it->first.empty() && it->first[0] <= 2) {
+            if (it->second) (void)hipGraphExecDestroy(it->second);
+            it = g.map.erase(it);
+        } else {
+            ++it;
+        }
+    }
+}
+
+// The 13-bit images (pack13.h) that the streaming GEMVs of the B <= 2 decode step read instead of the bf16 rows:
+// every layer's gate|up (one 2 I x H tensor) and down, and the tied embedding as lm_head reads it -- 2 L + 1
+// candidate tensors, 13/16 of their bytes (3.80 GB beside the resident bf16 weights at the 3B shapes).  (Re)built
+// on stream s by the first such step after a pgmi_prepare, outside any capture: pass one scans each tensor's
+// exponent range, the host reads the 2 L + 1 results (one stream synchronisation) and packs the tensors that fit;
+// a tensor that does not fit keeps the bf16 kernel, as does a whole kind whose buffer cannot be allocated.
+static int ensure_pk_image(pgmi_ctx* x, hipStream_t s, int B) {
+    const int want = pk_mask_for(x, B) & ~x->pk_done;
+    if (!want) return 0;
+    const pgmi_config& c = x->c;
+    // the PK kernels are the K = 2048 / K = 16384 forms
+    if (c.t_hidden != 2048 || c.t_intermediate != 16384) {
+        x->pk_done |= want;
+        return 0;
+    }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return 0;  // a caller's capture: this step reads the bf16 rows, a later one builds the image
+    }
+    const int L = c.t_layers;
+    const int64_t I = c.t_intermediate, H = c.t_hidden, V = c.t_vocab;
+    struct Cand { int kind; const uint16_t* W; int64_t rows, K; PkW* dst; uint8_t* out; };
+    std::vector<Cand> cands;
+    const int64_t gu_b = pk_image_bytes(2 * I, H), dn_b = pk_image_bytes(H, I), em_b = pk_image_bytes(V, H);
+    const int64_t kind_bytes[3] = {gu_b * L, dn_b * L, em_b};
+    int got = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!(want & (1 << k)) || kind_bytes[k] == 0) continue;
+        if (!x->pk_buf[k]) {
+            void* p = nullptr;
+            if (hipMalloc(&p, (size_t)kind_bytes[k]) != hipSuccess) {
+                (void)hipGetLastError();  // out of memory: this kind keeps the bf16 kernels
+                x->pk_alloc_failed = true;
+                continue;
+            }
+            x->allocs.push_back(p);
+            x->pk_buf[k] = reinterpret_cast<uint8_t*>(p);
+        }
+        got |= 1 << k;
+    }
+    for (int i = 0; i < L; ++i) {
+        TextLayerW& w = x->w.t[i];
+        if (got & PK_GATE_UP) cands.push_back({PK_GATE_UP, w.gate_up, 2 * I, H, &w.pk_gate_up, x->pk_buf[0] + gu_b * i});
+        if (got & PK_DOWN) cands.push_back({PK_DOWN, w.down, H, I, &w.pk_down, x->pk_buf[1] + dn_b * i});
+    }
+    if (got & PK_LM_HEAD) cands.push_back({PK_LM_HEAD, x->w.embed, V, H, &x->w.pk_embed, x->pk_buf[2]});
+    if (!cands.empty()) {
+        const size_t n = cands.size(), cap_n = (size_t)2 * L + 1;
+        if (!x->pk_stat) {
+            void* p = nullptr;
+            HIPCHK(hipMalloc(&p, cap_n * 2 * sizeof(unsigned)));
+            x->allocs.push_back(p);
+            x->pk_stat = reinterpret_cast<unsigned*>(p);
+        }
+        // stat[2 t] = largest exponent field (from 0), stat[2 t + 1] = smallest one >= 1 (from 0xFFFFFFFF)
+        std::vector<unsigned> st(2 * n);
+        for (size_t t = 0; t < n; ++t) { st[2 * t] = 0; st[2 * t + 1] = 0xFFFFFFFFu; }
+        HIPCHK(hipMemcpyAsync(x->pk_stat, st.data(), st.size() * sizeof(unsigned), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));  // (st is reused below)
+        for (size_t t = 0; t < n; ++t) pk_scan(s, cands[t].W, (long)(cands[t].rows * cands[t].K), x->pk_stat + 2 * t);
+        LAUNCHCHK();
+        HIPCHK(hipMemcpyAsync(st.data(), x->pk_stat, st.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (size_t t = 0; t < n; ++t) {
+            const int e_hi = (int)st[2 * t], e_lo = st[2 * t + 1] > 255u ? 256 : (int)st[2 * t + 1];
+            if (!pk_fits(e_hi, e_lo)) {
+                *cands[t].dst = PkW{};
+                continue;
+            }
+            pk_pack(s, cands[t].W, (long)cands[t].rows, (int)cands[t].K, e_hi, cands[t].out);
+            cands[t].dst->img = cands[t].out;
+            cands[t].dst->base2 = pk_base2(e_hi);
+        }
+        LAUNCHCHK();
+    }
+    x->pk_done |= want;
+    drop_small_batch_graphs(x->dgraphs);  // steps captured before held the bf16 launches
+    return 0;
+}
+
+int pgmi_set_decode_packed(pgmi_ctx* x, int on) {
+    if (!x) return fail(PGMI_E_ARG, "null context");
+    if (on > PK_ALL) return fail(PGMI_E_ARG, "decode_packed: 0 off, 1..7 a mask of kinds (1 gate|up, 2 down, 4 lm_head), < 0 default");
+    x->pk_mask = on < 0 ? -1 : on;
+    drop_small_batch_graphs(x->dgraphs);  // captured steps hold the other form's launches
+    x->pgraphs.clear();                   // (a last-row-only prefill's GEMVs follow the setting)
+    return 0;
+}
+
+int pgmi_decode_packed_info(const pgmi_ctx* x, int64_t* info, int n) {
+    if (!x || !info) return fail(PGMI_E_ARG, "null argument");
+    if (n < PGMI_PACKED_INFO_N) return fail(PGMI_E_ARG, "info needs PGMI_PACKED_INFO_N entries");
+    const pgmi_config& c = x->c;
+    const int64_t I = c.t_intermediate, H = c.t_hidden, V = c.t_vocab;
+    const bool shapes = H == 2048 && I == 16384;
+    int64_t np = 0, nr = 0, bp = 0, br = 0;
+    auto count = [&](int kind, const PkW& w, int64_t rows, int64_t K) {
+        if ((pk_mask_for(x, 1) & x->pk_done & kind) && w.img && shapes) { ++np; bp += pk_image_bytes(rows, K); }
+        else { ++nr; br += rows * K * 2; }
+    };
+    for (size_t i = 0; i < x->w.t.size(); ++i) {
+        count(PK_GATE_UP, x->w.t[i].pk_gate_up, 2 * I, H);
+        count(PK_DOWN, x->w.t[i].pk_down, H, I);
+    }
+    count(PK_LM_HEAD, x->w.pk_embed, V, H);
+    info[0] = pk_mask_for(x, 1); info[8] = pk_mask_for(x, 2); info[1] = np; info[2] = nr; info[3] = bp; info[4] = br;
+    info[5] = x->pk_alloc_failed; info[6] = x->mfw_alloc_failed; info[7] = x->pk_done;
+    return 0;
+}
+
+int pgmi_decode_packed_tensor(const pgmi_ctx* x, int kind, int layer) {
+    if (!x) return fail(PGMI_E_ARG, "null context");
+    if (kind != PK_GATE_UP && kind != PK_DOWN && kind != PK_LM_HEAD) return fail(PGMI_E_ARG, "kind: 1 gate|up, 2 down, 4 lm_head");
+    if (kind != PK_LM_HEAD && (layer < 0 || layer >= (int)x->w.t.size())) return fail(PGMI_E_ARG, "layer out of range");
+    const PkW& w = kind == PK_LM_HEAD ? x->w.pk_embed : kind == PK_GATE_UP ? x->w.t[layer].pk_gate_up : x->w.t[layer].pk_down;
+    return (pk_mask_for(x, 1) & x->pk_done & kind) && w.img ? 1 : 0;
+}
+
+// The format on the host, for tests (no device): e_hi / fit of n bf16 values, their image and its decode through
+// the very functions the kernels use (pack13.h).  rows x K values, K a multiple of 2048.
+int pgmi_pack13_scan(const uint16_t* w, int64_t n, int* e_hi, int* fits) {
+    if (!w || !e_hi || !fits) return fail(PGMI_E_ARG, "null argument");
+    if (n < 1) return fail(PGMI_E_ARG, "pack13: no values");
+    int hi = 0, lo = 256;
+    for (int64_t i = 0; i < n; ++i) {
+        const int ex = (w[i] >> 7) & 0xFF;
+        hi = std::max(hi, ex);
+        if (ex) lo = std::min(lo, ex);
+    }
+    *e_hi = hi;
+    *fits = pk_fits(hi, lo) ? 1 : 0;
+    return 0;
+}
+
+int64_t pgmi_pack13_bytes(int64_t rows, int64_t K) {
+    if (rows < 1 || K < kPkSegK || K % kPkSegK != 0) return -1;
+    return pk_image_bytes(rows, K);
+}
+
+static const uint8_t* pk_host_seg(const uint8_t* image, int64_t seg) { return image + seg * kPkSegBytes; }
+
+int pgmi_pack13_encode(const uint16_t* w, int64_t rows, int64_t K, int e_hi, uint8_t* image) {
+    if (!w || !image) return fail(PGMI_E_ARG, "null argument");
+    if (pgmi_pack13_bytes(rows, K) < 0) return fail(PGMI_E_ARG, "pack13: K must be a positive multiple of 2048, rows >= 1");
+    if (e_hi < 0 || e_hi > 255) return fail(PGMI_E_ARG, "pack13: e_hi is an exponent field (0..255)");
+    for (int64_t seg = 0; seg < rows * (K / kPkSegK); ++seg)
+        for (int l = 0; l < 64; ++l) {
+            uint4 f[4];
+            for (int ch = 0; ch < 4; ++ch) std::memcpy(&f[ch], w + seg * kPkSegK + 512 * ch + 8 * l, 16);
+            const PkSeg sg = pk_encode(f, e_hi);
+            uint8_t* d = image + seg * kPkSegBytes;
+            std::memcpy(d + pk_off_a(l), &sg.a, 16);
+            std::memcpy(d + pk_off_b(l), &sg.b, 16);
+            std::memcpy(d + pk_off_n(l), &sg.n, 16);
+            std::memcpy(d + pk_off_h(l), &sg.h, 4);
+        }
+    return 0;
+}
+
+int pgmi_pack13_decode(const uint8_t* image, int64_t rows, int64_t K, int e_hi, uint16_t* w) {
+    if (!w || !image) return fail(PGMI_E_ARG, "null argument");
+    if (pgmi_pack13_bytes(rows, K) < 0) return fail(PGMI_E_ARG, "pack13: K must be a positive multiple of 2048, rows >= 1");
+    if (e_hi < 0 || e_hi > 255) return fail(PGMI_E_ARG, "pack13: e_hi is an exponent field (0..255)");
+    const unsigned b2 = pk_base2(e_hi);
+    for (int64_t seg = 0; seg < rows * (K / kPkSegK); ++seg)
+        for (int l = 0; l < 64; ++l) {
+            const uint8_t* d = pk_host_seg(image, seg);
+            PkSeg sg;
+            std::memcpy(&sg.a, d + pk_off_a(l), 16);
+            std::memcpy(&sg.b, d + pk_off_b(l), 16);
+            std::memcpy(&sg.n, d + pk_off_n(l), 16);
+            std::memcpy(&sg.h, d + pk_off_h(l), 4);
+            for (int ch = 0; ch < 4; ++ch) {
+                const uint4 f = pk_chunk(sg, ch, b2);
+                std::memcpy(w + seg * kPkSegK + 512 * ch + 8 * l, &f, 16);
+            }
+        }
     return 0;
 }
 
@@ -1275,6 +1515,7 @@ static int decode_step(pgmi_ctx* x, const int64_t* ids, const void* embeds, int 
     if ((!ids && !embeds) || !kv || !logits) return fail(PGMI_E_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;
     if (B >= gemv_mf_min_batch() && (rc = ensure_mf_image(x, s))) return rc;
+    if (B < gemv_mf_min_batch() && (rc = ensure_pk_image(x, s, B))) return rc;
     int masked = 0;
     if (dev) {
         // position read on the device; the host no longer knows it, so the next call sets the state again
@@ -1577,20 +1818,45 @@ int pgmi_decode_kernel(pgmi_ctx* x, int which, int layer, int B, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const float eps = c.t_rms_eps;
     const int H = c.t_hidden;
+    // which 2, 3 and 4 read what the decode step reads: the 13-bit images at B <= 2 (pgmi_set_decode_packed)
+    if (which >= 2 && B < gemv_mf_min_batch() && (rc = ensure_pk_image(x, s, B))) return rc;
     const TextLayerW& w = x->w.t[layer];
     switch (which) {
         case 1: gemv_res(s, B, c.t_heads * c.t_head_dim, x->dAO, w.o, H, x->dH, x->ws); break;
-        case 2: gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT); break;
-        case 3: gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws); break;
+        case 2:
+            gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
+                       pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
+            break;
+        case 3:
+            gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws, pk_use(x, B, PK_DOWN, w.pk_down));
+            break;
         case 4: {
             int nparts = 0;
             gemv_logits(s, B, x->dH, x->w.final_norm, eps, x->w.embed, c.t_vocab, x->dlogits, x->pmax, x->pidx,
-                        &nparts);
+                        &nparts, nullptr, nullptr, nullptr, nullptr, 1, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed));
             break;
         }
         default: return fail(PGMI_E_ARG, "unknown kernel id");
     }
     LAUNCHCHK();
+    return 0;
+}
+
+int pgmi_debug_decode_buffer(pgmi_ctx* x, int which, void* buf, int64_t bytes, int write, void* stream) {
+    int rc;
+    if (!x || !buf) return fail(PGMI_E_ARG, "null argument");
+    if ((rc = ensure_prepared(x))) return rc;
+    const pgmi_config& c = x->c;
+    void* p;
+    int64_t cap;
+    switch (which) {
+        case 0: p = x->dH; cap = (int64_t)c.max_batch * c.t_hidden * 2; break;
+        case 1: p = x->dACT; cap = (int64_t)c.max_batch * c.t_intermediate * 2; break;
+        case 2: p = x->dlogits; cap = (int64_t)c.max_batch * c.t_vocab * 4; break;
+        default: return fail(PGMI_E_ARG, "decode buffer: 0 h, 1 act, 2 logits");
+    }
+    if (bytes < 1 || bytes > cap) return fail(PGMI_E_ARG, "decode buffer: byte count outside the buffer");
+    HIPCHK(hipMemcpyAsync(write ? p : buf, write ? buf : p, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 

@@ -20,6 +20,7 @@
 #include "coh.h"
 #include "common.h"
 #include "launch.h"
+#include "pack13.h"
 
 namespace pgmi {
 
@@ -77,6 +78,10 @@ struct GemvArgs {
     // batched decode (MFMA forms): the weight matrix's fragment-major image (k_mf_swizzle, built at prepare),
     // read instead of W when set (gate|up: the gate rows' image, then the up rows')
     const uint16_t* Wf;
+    // batch 1-2 (the PK kernels): the weight matrix's 13-bit image (pack13.h), read instead of W, and its
+    // per-tensor exponent base pk_base2(e_hi)
+    const uint8_t* Wp;
+    unsigned pk_base2;
 };
 
 // WK waves split one unit group's K range (WK = 4 for the 16384-wide down_proj), their
@@ -86,8 +91,14 @@ struct GemvArgs {
 // B * K/(512*WK) chunks fit in 32 VGPRs.  Otherwise the activation is staged in LDS.
 // RG (GV_QKV, GV_ORES): the ragged step -- every batch row reads its own step record (RoPE row, KV-append
 // row, chunk count); the lock-step kernels (RG = false) read record 0 once and compile to what they were.
-template <int B, int KCH, int RPW, int MODE, int WK, bool XREG, int DEPTH = 1, bool EMB = false, bool RG = false>
+// PK (the streaming modes GV_GEGLU, GV_RES with WK = 4, GV_LOGITS at B <= 2): the weights come from the 13-bit
+// image a.Wp (pack13.h), 52 instead of 64 bytes per lane and 2048 weights; each fragment is rebuilt bit for bit
+// right before its dot8, so the accumulation -- and every output -- is the bf16 kernel's.
+template <int B, int KCH, int RPW, int MODE, int WK, bool XREG, int DEPTH = 1, bool EMB = false, bool RG = false,
+          bool PK = false>
 __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, const int nblk, uint16_t* xs) {
+    static_assert(!PK || ((MODE == GV_GEGLU || MODE == GV_RES || MODE == GV_LOGITS) && (KCH / WK) % 4 == 0 && DEPTH == 1),
+                  "13-bit image: the streaming modes, whole 2048-weight segments per wave");
     static_assert(!EMB || (MODE == GV_QKV && XREG && WK == 1), "embedding fold: register-held q|k|v input only");
     static_assert(!RG || MODE == GV_QKV || MODE == GV_ORES, "per-row step records: q|k|v and o_proj only");
     constexpr int NR = (MODE == GV_QKV || MODE == GV_GEGLU) ? 2 : 1;
@@ -122,7 +133,9 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
 
     // DEPTH register sets of weight rows: groups g+1 .. g+DEPTH-1 stay in flight while group g
     // is reduced (statically indexed: the loop below is unrolled by DEPTH)
-    uint4 w[DEPTH][NL];
+    constexpr int NSEG = PK ? KCW / 4 : 1;  // PK: 2048-weight segments per wave and row
+    uint4 w[PK ? 1 : DEPTH][PK ? 1 : NL];
+    PkSeg wp[PK ? RPW * NR * NSEG : 1];
     auto issue = [&](auto slot, int base) {
         constexpr int SL = decltype(slot)::value;
 #pragma unroll
@@ -131,10 +144,24 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
             if (u >= bend) u = bend - 1;  // clamp: duplicate work, result discarded
 #pragma unroll
             for (int j = 0; j < NR; ++j) {
-                const uint16_t* rp = a.W + row_of(u, j) * K + kofs;
+                if constexpr (PK) {
+                    // the row's segments of this wave's K slice: three 16-B loads and one 4-B load per lane
+                    const uint8_t* sp = a.Wp + (row_of(u, j) * (KCH / 4) + wk * NSEG) * (long)kPkSegBytes;
 #pragma unroll
-                for (int c = 0; c < KCW; ++c)
-                    w[SL][(i * NR + j) * KCW + c] = kSmallTemporal ? ldg16(rp + 512 * c) : ldg_nt(rp + 512 * c);
+                    for (int g = 0; g < NSEG; ++g) {
+                        PkSeg& d = wp[(i * NR + j) * NSEG + g];
+                        const uint8_t* q = sp + g * kPkSegBytes;
+                        d.a = ldg_nt(q + pk_off_a(lane));
+                        d.b = ldg_nt(q + pk_off_b(lane));
+                        d.n = ldg_nt(q + pk_off_n(lane));
+                        d.h = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(q + pk_off_h(lane)));
+                    }
+                } else {
+                    const uint16_t* rp = a.W + row_of(u, j) * K + kofs;
+#pragma unroll
+                    for (int c = 0; c < KCW; ++c)
+                        w[SL][(i * NR + j) * KCW + c] = kSmallTemporal ? ldg16(rp + 512 * c) : ldg_nt(rp + 512 * c);
+                }
             }
         }
     };
@@ -394,6 +421,12 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
                 for (int b = 0; b < B; ++b) acc[i][j][b] = 0.f;
 #pragma unroll
         for (int c = 0; c < KCW; ++c) {
+            // PK: chunk c of every row, rebuilt from its segment (the same dwords the bf16 load delivers)
+            uint4 wc[PK ? RPW * NR : 1];
+            if constexpr (PK) {
+#pragma unroll
+                for (int r = 0; r < RPW * NR; ++r) wc[r] = pk_chunk(wp[r * NSEG + c / 4], c % 4, a.pk_base2);
+            }
 #pragma unroll
             for (int b = 0; b < B; ++b) {
                 uint4 xv;
@@ -402,7 +435,10 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
 #pragma unroll
                 for (int i = 0; i < RPW; ++i)
 #pragma unroll
-                    for (int j = 0; j < NR; ++j) acc[i][j][b] = dot8(w[SL][(i * NR + j) * KCW + c], xv, acc[i][j][b]);
+                    for (int j = 0; j < NR; ++j) {
+                        if constexpr (PK) acc[i][j][b] = dot8(wc[i * NR + j], xv, acc[i][j][b]);
+                        else acc[i][j][b] = dot8(w[SL][(i * NR + j) * KCW + c], xv, acc[i][j][b]);
+                    }
             }
         }
         const int cur = ub;
@@ -594,10 +630,11 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
     }
 }
 
-template <int B, int KCH, int RPW, int MODE, int WK, bool XREG, int DEPTH, bool EMB = false, bool RG = false>
+template <int B, int KCH, int RPW, int MODE, int WK, bool XREG, int DEPTH, bool EMB = false, bool RG = false,
+          bool PK = false>
 __global__ void __launch_bounds__(256) k_gemv(GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [B][K]
-    gemv_block<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG>(a, blockIdx.x, gridDim.x, xs);
+    gemv_block<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG, PK>(a, blockIdx.x, gridDim.x, xs);
 }
 
 }  // namespace pgmi

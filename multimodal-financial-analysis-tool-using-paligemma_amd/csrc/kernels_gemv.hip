@@ -31,13 +31,13 @@ hipError_t launch_error_take(const char** what) {
     return e;
 }
 
-template <int B, int KCH, int RPW, int MODE, int WK = 1, int DEPTH = 1, bool EMB = false, bool RG = false>
+template <int B, int KCH, int RPW, int MODE, int WK = 1, int DEPTH = 1, bool EMB = false, bool RG = false, bool PK = false>
 static void launch_gemv(hipStream_t s, const GemvArgs& a, int max_blocks = 0) {
     constexpr bool XREG = (MODE != GV_ORES) && B * (KCH / WK) <= 8;
     size_t lds = XREG ? 0 : (size_t)B * KCH * 512 * sizeof(uint16_t);
     static size_t attr = 0;  // largest dynamic LDS size granted so far
     if (lds > attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG, PK>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             launch_error_set(e, "k_gemv: dynamic LDS size");
@@ -48,7 +48,14 @@ static void launch_gemv(hipStream_t s, const GemvArgs& a, int max_blocks = 0) {
     constexpr int per_block = (4 / WK) * RPW;
     int blocks = (a.n_units + per_block - 1) / per_block;
     if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
-    hipLaunchKernelGGL((k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG>), dim3(blocks), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((k_gemv<B, KCH, RPW, MODE, WK, XREG, DEPTH, EMB, RG, PK>), dim3(blocks), dim3(256), lds, s, a);
+}
+
+// the same launch reading the weights' 13-bit image (a.Wp set) or their bf16 rows: one grid, one LDS size
+template <int B, int KCH, int RPW, int MODE, int WK = 1>
+static void launch_gemv_pk(hipStream_t s, const GemvArgs& a, int max_blocks = 0) {
+    if (a.Wp) launch_gemv<B, KCH, RPW, MODE, WK, 1, false, false, true>(s, a, max_blocks);
+    else launch_gemv<B, KCH, RPW, MODE, WK>(s, a, max_blocks);
 }
 
 // K = 2048 (hidden); nh q heads, nkv kv heads of 256
@@ -83,7 +90,7 @@ void gemv_qkv(hipStream_t s, int B, int nh, int nkv, const uint16_t* h, const ui
 }
 
 void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W, int N, uint16_t* h_inout,
-              float* ws) {
+              float* ws, PkW pk) {
     GemvArgs a{};
     a.x = x; a.norm_w = nullptr; a.W = W; a.n_units = N; a.K = K; a.nb = B; a.out = h_inout;
     if (B >= gemv_mf_min_batch() && K % 128 == 0 && ws) {
@@ -108,8 +115,10 @@ void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W,
             GemvArgs c = a;
             c.x = x + (long)b0 * K; c.out = h_inout + (long)b0 * N; c.nb = nb;
             // K split in 4 inside the workgroup: 512 workgroups of one row each
-            if (nb <= 1) launch_gemv<1, 32, 1, GV_RES, 4>(s, c, 512);
-            else if (nb <= 2) launch_gemv<2, 32, 2, GV_RES, 4>(s, c);
+            // B <= 2 (one pass, b0 = 0): the 13-bit image when the caller has one
+            if (B <= 2 && K == 16384) { c.Wp = pk.img; c.pk_base2 = pk.base2; }
+            if (nb <= 1) launch_gemv_pk<1, 32, 1, GV_RES, 4>(s, c, 512);
+            else if (nb <= 2) launch_gemv_pk<2, 32, 2, GV_RES, 4>(s, c);
             else launch_gemv<4, 32, 2, GV_RES, 4>(s, c);
         }
     }
@@ -155,7 +164,7 @@ void gemv_o_attn(hipStream_t s, int B, int G, const float* part, int max_chunks,
 }
 
 void gemv_geglu(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w, float eps, const uint16_t* Wgu,
-                int I, uint16_t* act, float* ssq, const uint16_t* Wf) {
+                int I, uint16_t* act, float* ssq, const uint16_t* Wf, PkW pk) {
     GemvArgs a{};
     a.x = h; a.norm_w = norm_w; a.eps = eps; a.W = Wgu; a.n_units = I; a.K = 2048; a.nb = B; a.I = I; a.out = act;
     if (B >= gemv_mf_min_batch()) {
@@ -164,8 +173,9 @@ void gemv_geglu(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w,
         gemv_mf_geglu(s, a);
         return;
     }
-    if (B <= 1) launch_gemv<1, 4, 1, GV_GEGLU>(s, a, 1024);
-    else L_(2, 4, 2, GV_GEGLU);  // B >= 3 runs on MFMA (above)
+    a.Wp = pk.img; a.pk_base2 = pk.base2;
+    if (B <= 1) launch_gemv_pk<1, 4, 1, GV_GEGLU>(s, a, 1024);
+    else launch_gemv_pk<2, 4, 2, GV_GEGLU>(s, a);  // B >= 3 runs on MFMA (above)
 }
 
 int gemv_logits_blocks() { return 2048; }
@@ -175,7 +185,7 @@ bool gemv_logits_folds(int B) { return B < gemv_mf_min_batch(); }
 
 bool gemv_logits(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w, float eps, const uint16_t* E,
                  int V, float* logits, float* pmax, int* pidx, int* nparts, unsigned* done, int64_t* next,
-                 StepState* adv, int64_t* hist, int adv_n) {
+                 StepState* adv, int64_t* hist, int adv_n, PkW pk) {
     GemvArgs a{};
     a.x = h; a.norm_w = norm_w; a.eps = eps; a.W = E; a.n_units = V; a.K = 2048; a.nb = B; a.logits = logits;
     a.pmax = pmax; a.pidx = pidx;
@@ -185,6 +195,7 @@ bool gemv_logits(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w
         *nparts = gemv_mf_logits(s, a, mb);
         return false;
     }
+    a.Wp = pk.img; a.pk_base2 = pk.base2;
     const bool fold = done && next && gemv_logits_folds(B);
     if (fold) {
         a.done = done;
@@ -197,7 +208,7 @@ bool gemv_logits(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w
     do {                                                                \
         blocks = (V + 4 * rpw - 1) / (4 * rpw);                         \
         if (blocks > mb) blocks = mb;                                   \
-        launch_gemv<b_, 4, rpw, GV_LOGITS>(s, a, mb);                   \
+        launch_gemv_pk<b_, 4, rpw, GV_LOGITS>(s, a, mb);                \
     } while (0)
     if (B <= 1) LG_(1, 4);
     else LG_(2, 4);  // B >= 3 runs on MFMA (above)

@@ -116,9 +116,19 @@ void gemv_qkv(hipStream_t s, int B, int nh, int nkv, const uint16_t* h, const ui
               uint16_t* q_out, uint16_t* kc, uint16_t* vc, long kv_b_stride, float* ws = nullptr,
               const EmbedFold* emb = nullptr, const uint16_t* Wf = nullptr,  // Wf: as gemv_geglu's
               int st_stride = 0);
+// The 13-bit image of a weight matrix (pack13.h) for the streaming GEMVs at B <= 2 (gate|up, down at K = 16384,
+// lm_head): img null = read the bf16 rows; base2 = pk_base2(e_hi).  Same outputs, bit for bit, either way.
+struct PkW {
+    const uint8_t* img = nullptr;
+    unsigned base2 = 0;
+};
+// pass one / two of the image build (kernels_pack.hip): stat[0] = largest exponent field, stat[1] = smallest
+// one >= 1 (caller presets 0 / 0xFFFFFFFF); out: pk_image_bytes(rows, K) bytes, K a multiple of 2048
+void pk_scan(hipStream_t s, const uint16_t* W, long numel, unsigned* stat);
+void pk_pack(hipStream_t s, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out);
 // ws: fp32 scratch (>= 4 x B x N floats) for the MFMA path's K split of K = 16384 (B >= 3)
 void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W, int N, uint16_t* h_inout,
-              float* ws);
+              float* ws, PkW pk = {});
 // gemv_res, then hn = RMSNorm(h) with norm_w (nullptr: none); on the batched MFMA path the norm is
 // fused into the K-split combine (one workgroup per row)
 void gemv_res_norm(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W, int N, uint16_t* h_inout,
@@ -139,7 +149,8 @@ void gemv_o_attn(hipStream_t s, int B, int G, const float* part, int max_chunks,
 // partials gemv_o_attn wrote instead of the row pass; Wf (idem): the gate|up weights' fragment-major
 // image (mf_swizzle: the gate rows', then the up rows'), read instead of Wgu
 void gemv_geglu(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w, float eps,
-                const uint16_t* Wgu, int I, uint16_t* act, float* ssq = nullptr, const uint16_t* Wf = nullptr);
+                const uint16_t* Wgu, int I, uint16_t* act, float* ssq = nullptr, const uint16_t* Wf = nullptr,
+                PkW pk = {});
 int gemv_logits_blocks();
 int gemv_mf_min_batch();  // smallest batch on the MFMA decode projections
 // done/next/adv (decode, may be null): fold the argmax into the launch's last workgroup and
@@ -147,7 +158,7 @@ int gemv_mf_min_batch();  // smallest batch on the MFMA decode projections
 bool gemv_logits(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w, float eps,
                  const uint16_t* E, int V, float* logits, float* pmax, int* pidx, int* nparts,
                  unsigned* done = nullptr, int64_t* next = nullptr, StepState* adv = nullptr,
-                 int64_t* hist = nullptr, int adv_n = 1);
+                 int64_t* hist = nullptr, int adv_n = 1, PkW pk = {});
 // adv (may be null): the decode step state, advanced by one step (the step's last kernel); hist (may be
 // null): a second destination of the argmax (a multi-step graph's per-step token record)
 void argmax_finish(hipStream_t s, int B, const float* pmax, const int* pidx, int nparts, int64_t* out,

@@ -73,6 +73,13 @@ SIGNATURES = {
     "pgmi_set_prefill_graph": (i32, [vp, i32]),
     "pgmi_graph_count": (i32, [vp, i32]),
     "pgmi_set_decode_staged_norm": (i32, [vp, i32]),
+    "pgmi_set_decode_packed": (i32, [vp, i32]),
+    "pgmi_decode_packed_info": (i32, [vp, ctypes.POINTER(i64), i32]),
+    "pgmi_decode_packed_tensor": (i32, [vp, i32, i32]),
+    "pgmi_pack13_scan": (i32, [vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+    "pgmi_pack13_bytes": (i64, [i64, i64]),
+    "pgmi_pack13_encode": (i32, [vp, i64, i64, i32, vp]),
+    "pgmi_pack13_decode": (i32, [vp, i64, i64, i32, vp]),
     "pgmi_prefill_kernel": (i32, [vp, i32, i32, i32, vp]),
     "pgmi_debug_gemm_tiles": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "pgmi_debug_gemm_plan": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
@@ -91,6 +98,7 @@ SIGNATURES = {
     "pgmi_broadcast_weights": (i32, [vp, vp, i32, vp]),
     "pgmi_eos_update": (i32, [vp, vp, vp, i32, i64, i64, vp, vp]),
     "pgmi_decode_kernel": (i32, [vp, i32, i32, i32, vp]),
+    "pgmi_debug_decode_buffer": (i32, [vp, i32, vp, i64, i32, vp]),
     "pgmi_tune_gemm": (i32, [i32, i32]),
     "pgmi_tune_gemm_shape": (i32, [i32, i32, i32, i32, i32, i32]),
     "pgmi_tune_attention": (i32, [i32]),
@@ -124,7 +132,12 @@ def lib():
             raise NativeError(f"{LIB_PATH} not built: run `make -C csrc` or __graft_entry__.build()")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                if os.environ.get("PGMI_LIB_PATH"):
+                    continue  # an older build under A/B: the entries it lacks stay unbound
+                raise
             fn.restype = res
             fn.argtypes = args
         _lib = L

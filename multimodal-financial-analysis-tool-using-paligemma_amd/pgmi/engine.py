@@ -526,6 +526,40 @@ class Engine:
         """Batched decode RMSNorm form: 0 once per row (default), 1 staged per projection, -1 default."""
         N.check(self.lib.pgmi_set_decode_staged_norm(self.ctx, int(on)), "pgmi_set_decode_staged_norm")
 
+    def set_decode_packed(self, on: int) -> None:
+        """Decode at batch 1-2 on the lossless 13-bit weight images: 0 off, a mask of kinds (1 gate|up, 2 down,
+        4 lm_head; 7 all), -1 the default (all at B = 1, lm_head at B = 2).  Results are bit-identical either way (pgmi_set_decode_packed)."""
+        N.check(self.lib.pgmi_set_decode_packed(self.ctx, int(on)), "pgmi_set_decode_packed")
+
+    def decode_packed_info(self) -> dict:
+        """How the batch 1-2 decode step reads its 2 x layers + 1 streamed tensors now (pgmi_decode_packed_info)."""
+        v = (ctypes.c_int64 * 9)()
+        N.check(self.lib.pgmi_decode_packed_info(self.ctx, v, 9), "pgmi_decode_packed_info")
+        return {"mask": v[0], "mask_b2": v[8], "packed": v[1], "raw": v[2], "packed_bytes": v[3], "raw_bytes": v[4],
+                "alloc_failed": bool(v[5]), "mf_alloc_failed": bool(v[6]), "scanned": v[7]}
+
+    def decode_packed_tensor(self, kind: int, layer: int = 0) -> bool:
+        """Is the tensor of kind 1 gate|up / 2 down (of `layer`) / 4 lm_head read from its 13-bit image now?"""
+        rc = self.lib.pgmi_decode_packed_tensor(self.ctx, int(kind), int(layer))
+        if rc < 0:
+            N.check(rc, "pgmi_decode_packed_tensor")
+        return rc == 1
+
+    def decode_kernel(self, which: int, layer: int, B: int) -> None:
+        """One decode projection on the decode workspace (pgmi_decode_kernel): 1 o_proj, 2 gate|up, 3 down, 4 lm_head."""
+        self._ready()
+        N.check(self.lib.pgmi_decode_kernel(self.ctx, int(which), int(layer), int(B), self._s()), "pgmi_decode_kernel")
+
+    def decode_buffer(self, which: int, t: torch.Tensor, write: bool = False) -> torch.Tensor:
+        """Copy the decode workspace's h (0) / act (1) / logits (2) rows into the contiguous device tensor t, or
+        (write) t into the workspace (pgmi_debug_decode_buffer: a test hook)."""
+        self._ready()
+        if t.device != self.device or not t.is_contiguous():
+            raise ValueError("decode_buffer: a contiguous tensor on the engine's device")
+        N.check(self.lib.pgmi_debug_decode_buffer(self.ctx, int(which), t.data_ptr(), t.numel() * t.element_size(),
+                                                  int(bool(write)), self._s()), "pgmi_debug_decode_buffer")
+        return t
+
     def argmax(self, logits: torch.Tensor) -> torch.Tensor:
         l2 = logits.reshape(-1, logits.shape[-1]).contiguous()
         out = torch.empty(l2.shape[0], dtype=torch.int64, device=self.device)
