@@ -247,6 +247,47 @@ int pgmi_pack13_scan(const uint16_t* w, int64_t n, int* e_hi, int* fits);
 int64_t pgmi_pack13_bytes(int64_t rows, int64_t K);
 int pgmi_pack13_encode(const uint16_t* w, int64_t rows, int64_t K, int e_hi, uint8_t* image);
 int pgmi_pack13_decode(const uint8_t* image, int64_t rows, int64_t K, int e_hi, uint16_t* w);
+/* ---- LoRA adapters (the product of the reference's fine-tuning workflow, SURVEY.md C13: a peft LoraConfig on
+ * q_proj / k_proj / v_proj; the PEFT helpers of modeling_gemma.py:458-466,551).  An adapter is merged into the
+ * weight slab when it is activated, so the forward kernels do not change and an active adapter costs nothing per
+ * token.  The rule (csrc/lora.h), for a target W[N][K] with factors A[r][K], B[N][r] and a scale s in fp32:
+ *     acc = 0; for j = 0 .. r-1: acc = acc + (B[n][j] * A[j][k])   (fp32 multiply, then fp32 add: not fused)
+ *     W'[n][k] = bf16_rne(fp32(W[n][k]) + acc * s)
+ * with W the PRISTINE base every time: one rounding, and switching adapters any number of times cannot drift.
+ *   - Up to PGMI_LORA_MAX adapters per context; their factors stay resident on the device as fp32.
+ *   - Targets: the 2-D slab weight of any Linear module -- text q/k/v/o_proj and gate/up/down_proj, vision
+ *     q/k/v/out_proj, fc1 and fc2, multi_modal_projector.linear.  Embeddings, the 4-D patch convolution, norms,
+ *     biases and unknown names are PGMI_E_ARG, as is a factor whose shape does not match its target.
+ *   - pgmi_lora_add: a_shape = {r, K}, b_shape = {N, r}; r in [1, 256] is taken from the shapes.  Factors of dtype
+ *     PGMI_DTYPE_* in host or device memory (on_device) are widened to fp32 exactly.  Adding to the active adapter,
+ *     or a target the adapter already has, is refused (PGMI_E_STATE / PGMI_E_ARG).  Synchronises `stream`.
+ *   - pgmi_lora_set(id), id = -1 for the base model: synchronises the device on entry and `stream` on exit, as
+ *     pgmi_prepare does; PGMI_E_STATE inside a stream capture.  A target without a valid pristine copy is first
+ *     snapshotted (slab -> copy); targets of the outgoing adapter that the incoming one lacks are restored from
+ *     their copies; the incoming one's targets are merged copy -> slab.  After pgmi_lora_set(-1) the slab is bit
+ *     for bit what it was before the first activation.  Only what depends on a changed tensor is re-derived: the
+ *     fragment-major images (B >= 3) when a text-layer projection changed, the 13-bit images of gate|up / down
+ *     when a gate_proj or up_proj / a down_proj changed (a q/k/v adapter re-scans nothing); the RoPE tables and
+ *     the padded patch matrix never.  Captured graphs are kept where their launches stay valid.
+ *   - The pristine copies are forgotten by pgmi_prepare while no adapter is active (the base may have changed)
+ *     and by pgmi_bind_weights, which also deactivates; pgmi_prepare while one is active re-derives from the
+ *     slab as it is and keeps them.  pgmi_load_weight, pgmi_load_safetensors, pgmi_fill_synthetic and
+ *     pgmi_broadcast_weights are PGMI_E_STATE while an adapter is active: deactivate first.
+ *   - pgmi_lora_active: the active id, -1 for none (or a null context).  pgmi_lora_info: info[0] the adapter's
+ *     targets, [1] bytes of its resident factors, [2] bytes of its targets' pristine copies held now;
+ *     n >= PGMI_LORA_INFO_N. */
+#define PGMI_LORA_MAX 8
+#define PGMI_LORA_INFO_N 3
+int pgmi_lora_create(pgmi_ctx* ctx, int* id);
+int pgmi_lora_add(pgmi_ctx* ctx, int id, const char* weight_name, const void* A, int a_dtype, const int64_t* a_shape,
+                  const void* B, int b_dtype, const int64_t* b_shape, float scaling, int on_device, void* stream);
+int pgmi_lora_free(pgmi_ctx* ctx, int id);
+int pgmi_lora_set(pgmi_ctx* ctx, int id, void* stream);
+int pgmi_lora_active(const pgmi_ctx* ctx);
+int pgmi_lora_info(const pgmi_ctx* ctx, int id, int64_t* info, int n);
+/* The merge rule on the host (tests; no device): W, out bf16 [N][K], A fp32 [r][K], B fp32 [N][r]. */
+int pgmi_lora_merge_host(const uint16_t* W, int64_t N, int64_t K, const float* A, const float* B, int r,
+                         float scaling, uint16_t* out);
 /* lm_head + .float() of GemmaForCausalLM (modeling_gemma.py:417-418) over final-normed hidden
  * rows: logits (device fp32 [rows][vocab]) = fp32(bf16(normed . E^T)) with the tied embedding E.
  * Together with pgmi_lm_final_hidden this materialises the prefill's all-row logits on demand
@@ -419,6 +460,10 @@ int pgmi_op_rope(pgmi_ctx* ctx, const void* x, const void* cos_rows, const void*
                  int head_dim, void* out, void* stream);
 /* out = bf16(x * a) over n bf16 values (n a multiple of 8): GemmaModel's normalizer (modeling_gemma.py:367-368) */
 int pgmi_op_scale(pgmi_ctx* ctx, const void* x, float a, int64_t n, void* out, void* stream);
+/* the LoRA merge kernel on caller tensors (device; 16-B aligned): W, out bf16 [N][K] (not overlapping), A fp32
+ * [r][K], B fp32 [N][r]; K a multiple of 8, r in [1, 256].  Bit for bit pgmi_lora_merge_host. */
+int pgmi_op_lora_merge(pgmi_ctx* ctx, const void* W, int N, int K, const void* A, const void* B, int r,
+                       float scaling, void* out, void* stream);
 /* decode GEMV family on one layer's weights (tests): y[b][n] += W x (residual form); B in [1, 16], K 2048 or 16384 */
 int pgmi_op_gemv_res(pgmi_ctx* ctx, const void* x, const void* W, int B, int N, int K, void* h_inout,
                      void* stream);

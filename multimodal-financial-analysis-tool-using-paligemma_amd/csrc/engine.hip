@@ -22,6 +22,7 @@
 #include "../../include/pgmi.h"
 #include "common.h"
 #include "launch.h"
+#include "lora.h"
 #include "pack13.h"
 #include "safetensors_hdr.h"
 
@@ -104,6 +105,24 @@ enum { PK_GATE_UP = 1, PK_DOWN = 2, PK_LM_HEAD = 4, PK_ALL = 7 };
 // down are VALU-limited and lose 4 %, lm_head still gains 8 %)
 constexpr int kPkDefaultB1 = PK_ALL, kPkDefaultB2 = PK_LM_HEAD;
 
+// LoRA adapters (pgmi_lora_*): an adapter is a list of targets, each a slab weight with its resident fp32 factors
+struct LoraTarget {
+    int slot;        // index into pgmi_ctx::slots: a 2-D Linear weight [N][K]
+    int r;
+    float scaling;
+    float *A, *B;    // device fp32 [r][K], [N][r]
+};
+struct LoraAdapter {
+    bool used = false;
+    std::vector<LoraTarget> targets;
+    int64_t factor_bytes = 0;
+};
+// the pristine (base) copy of a slab weight some adapter was merged into; valid: it holds the base as of now
+struct LoraPristine {
+    uint16_t* copy = nullptr;
+    bool valid = false;
+};
+
 struct pgmi_ctx {
     pgmi_config c;
     int device;
@@ -180,6 +199,11 @@ struct pgmi_ctx {
     std::vector<hipEvent_t> probe_ev;
     bool probe_on = false;
     bool graph_before_probe = true;  // prefill_graph as the caller left it before the probe turned it off
+    // LoRA: the adapters, the one merged into the slab now (-1: none, the slab holds the base) and the pristine
+    // copies by slot (allocated at the first activation that needs them, owned here, not in `allocs`)
+    LoraAdapter lora[PGMI_LORA_MAX];
+    int lora_active = -1;
+    std::map<int, LoraPristine> lora_pristine;
 };
 
 namespace {
@@ -203,6 +227,43 @@ void pk_forget(pgmi_ctx* x) {
     x->w.pk_embed = PkW{};
     for (auto& t : x->w.t) t.pk_gate_up = t.pk_down = PkW{};
 }
+
+// forget the 13-bit images of the kinds in `kinds` alone (their tensors changed): the next B <= 2 step rescans
+// and repacks those, the other kinds' images stay
+void pk_forget_kinds(pgmi_ctx* x, int kinds) {
+    x->pk_done &= ~kinds;
+    for (auto& t : x->w.t) {
+        if (kinds & PK_GATE_UP) t.pk_gate_up = PkW{};
+        if (kinds & PK_DOWN) t.pk_down = PkW{};
+    }
+    if (kinds & PK_LM_HEAD) x->w.pk_embed = PkW{};
+}
+
+// does this context's batched decode (B >= 3) read fragment-major images at all
+bool mf_wanted(const pgmi_config& c) {
+    return c.max_batch >= gemv_mf_min_batch() && c.t_intermediate % 32 == 0 && c.t_hidden % 32 == 0;
+}
+
+bool ends_with(const std::string& s, const char* suffix) {
+    const size_t n = std::strlen(suffix);
+    return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+// a LoRA target: the 2-D weight of a Linear module (not an embedding, the patch convolution, a norm or a bias)
+bool lora_targetable(const Slot& s) {
+    if (s.ndim != 2) return false;
+    for (const char* m : {"q_proj.weight", "k_proj.weight", "v_proj.weight", "o_proj.weight", "out_proj.weight",
+                          "gate_proj.weight", "up_proj.weight", "down_proj.weight", "mlp.fc1.weight", "mlp.fc2.weight",
+                          "multi_modal_projector.linear.weight"})
+        if (ends_with(s.name, m)) return true;
+    return false;
+}
+
+void lora_forget_pristine(pgmi_ctx* x) {
+    for (auto& kv : x->lora_pristine) kv.second.valid = false;
+}
+
+const char* kLoraActiveMsg = "a LoRA adapter is merged into the weights: deactivate first (pgmi_lora_set(ctx, -1))";
 
 int n_img(const pgmi_config& c) { return (c.v_image / c.v_patch) * (c.v_image / c.v_patch); }
 
@@ -505,6 +566,9 @@ int pgmi_destroy(pgmi_ctx* x) {
     for (auto& e : x->probe_ev) (void)hipEventDestroy(e);
     x->dgraphs.clear();
     x->pgraphs.clear();
+    for (auto& a : x->lora)
+        for (auto& t : a.targets) { (void)hipFree(t.A); (void)hipFree(t.B); }
+    for (auto& kv : x->lora_pristine) (void)hipFree(kv.second.copy);
     for (void* p : x->allocs) (void)hipFree(p);
     if (x->cap_stream) (void)hipStreamDestroy(x->cap_stream);
     delete x;
@@ -528,6 +592,8 @@ int pgmi_bind_weights(pgmi_ctx* x, void* slab) {
     if (!x || !slab) return fail(PGMI_E_ARG, "null argument");
     if (reinterpret_cast<uintptr_t>(slab) % 256 != 0) return fail(PGMI_E_ARG, "weight slab must be 256-byte aligned");
     x->slab = reinterpret_cast<uint8_t*>(slab);
+    x->lora_active = -1;  // a new slab holds its own base: nothing is merged into it
+    lora_forget_pristine(x);
     pk_forget(x);
     x->dgraphs.clear();
     x->pgraphs.clear();
@@ -537,6 +603,7 @@ int pgmi_bind_weights(pgmi_ctx* x, void* slab) {
 int pgmi_load_weight(pgmi_ctx* x, const char* name, const void* src, int dtype, int on_device, void* stream) {
     if (!x || !name || !src) return fail(PGMI_E_ARG, "null argument");
     if (!x->slab) return fail(PGMI_E_STATE, "weights are not bound");
+    if (x->lora_active >= 0) return fail(PGMI_E_STATE, kLoraActiveMsg);
     auto it = x->index.find(name);
     if (it == x->index.end()) return fail(PGMI_E_ARG, std::string("unknown weight ") + name);
     const Slot& s = x->slots[it->second];
@@ -597,6 +664,7 @@ int pgmi_safetensors_entry(const char* path, int i, char* name, int name_cap, in
 int pgmi_load_safetensors(pgmi_ctx* x, const char* path, int* n_loaded, int* n_skipped, void* stream) {
     if (!x || !path) return fail(PGMI_E_ARG, "null argument");
     if (!x->slab) return fail(PGMI_E_STATE, "weights are not bound");
+    if (x->lora_active >= 0) return fail(PGMI_E_STATE, kLoraActiveMsg);
     HIPCHK(hipSetDevice(x->device));
     StFile f;
     if (!st_open(path, f)) return fail(PGMI_E_ARG, f.error);
@@ -678,6 +746,7 @@ uint64_t pgmi_synthetic_key(const char* name, uint64_t seed) { return splitmix64
 int pgmi_fill_synthetic(pgmi_ctx* x, const char* name, uint64_t key, float scale, float offset, void* stream) {
     if (!x || !name) return fail(PGMI_E_ARG, "null argument");
     if (!x->slab) return fail(PGMI_E_STATE, "weights are not bound");
+    if (x->lora_active >= 0) return fail(PGMI_E_STATE, kLoraActiveMsg);
     auto it = x->index.find(name);
     if (it == x->index.end()) return fail(PGMI_E_ARG, std::string("unknown weight ") + name);
     const Slot& s = x->slots[it->second];
@@ -774,9 +843,12 @@ int pgmi_prepare(pgmi_ctx* x) {
     // the batched decode's fragment-major weight images: built by the first decode step with B >= 3 after this
     // call (ensure_mf_image), not here -- a context that never decodes a batch (the drop-in's single-sequence
     // loop on its max_batch-8 context) neither allocates their 3.96 GB nor pays for the swizzle
-    x->mfw_dirty = c.max_batch >= gemv_mf_min_batch() && c.t_intermediate % 32 == 0 && c.t_hidden % 32 == 0;
+    x->mfw_dirty = mf_wanted(c);
     // the 13-bit images of the B <= 2 step likewise: rebuilt from the new weights by the next such step
     pk_forget(x);
+    // LoRA: with no adapter merged the base may have changed, so the pristine copies are taken anew at the next
+    // activation; with one merged the slab is derived from as it is and the copies still hold its base
+    if (x->lora_active < 0) lora_forget_pristine(x);
     std::vector<uint16_t> cs, sn;
     if (!x->host_cos.empty()) {
         cs = x->host_cos;
@@ -1488,6 +1560,230 @@ int pgmi_pack13_decode(const uint8_t* image, int64_t rows, int64_t K, int e_hi, 
     return 0;
 }
 
+// ---------------------------------------------------------------- LoRA adapters (pgmi.h; the rule: lora.h)
+static LoraAdapter* lora_get(pgmi_ctx* x, int id) {
+    return x && id >= 0 && id < PGMI_LORA_MAX && x->lora[id].used ? &x->lora[id] : nullptr;
+}
+
+static const LoraTarget* lora_find(const LoraAdapter* a, int slot) {
+    if (a)
+        for (const LoraTarget& t : a->targets)
+            if (t.slot == slot) return &t;
+    return nullptr;
+}
+
+int pgmi_lora_create(pgmi_ctx* x, int* id) {
+    if (!x || !id) return fail(PGMI_E_ARG, "null argument");
+    for (int i = 0; i < PGMI_LORA_MAX; ++i)
+        if (!x->lora[i].used) {
+            x->lora[i] = LoraAdapter{};
+            x->lora[i].used = true;
+            *id = i;
+            return 0;
+        }
+    return fail(PGMI_E_STATE, "a context holds at most " + std::to_string(PGMI_LORA_MAX) + " LoRA adapters: free one first");
+}
+
+// one factor to its resident fp32 form: host values are widened here, device values by k_lora_widen
+static int lora_upload(pgmi_ctx* x, hipStream_t st, const void* src, int dtype, int64_t n, int on_device, float** out) {
+    void* p = nullptr;
+    if (hipMalloc(&p, (size_t)n * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PGMI_E_NOMEM, "LoRA factor: hipMalloc of " + std::to_string(n * 4) + " bytes");
+    }
+    *out = reinterpret_cast<float*>(p);
+    if (on_device) {
+        lora_widen(st, src, dtype, (long)n, *out);
+        LAUNCHCHK();
+        return 0;
+    }
+    std::vector<float> tmp;
+    const float* h = reinterpret_cast<const float*>(src);
+    if (dtype != PGMI_DTYPE_F32) {
+        tmp.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i)
+            tmp[i] = dtype == PGMI_DTYPE_F16 ? (float)reinterpret_cast<const _Float16*>(src)[i]
+                                             : lora_bits_f((uint32_t)reinterpret_cast<const uint16_t*>(src)[i] << 16);
+        h = tmp.data();
+    }
+    HIPCHK(hipMemcpyAsync(*out, h, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // (tmp, and the caller's buffer, may go after the return)
+    return 0;
+}
+
+int pgmi_lora_add(pgmi_ctx* x, int id, const char* name, const void* A, int a_dtype, const int64_t* a_shape,
+                  const void* B, int b_dtype, const int64_t* b_shape, float scaling, int on_device, void* stream) {
+    if (!x || !name || !A || !B || !a_shape || !b_shape) return fail(PGMI_E_ARG, "null argument");
+    LoraAdapter* a = lora_get(x, id);
+    if (!a) return fail(PGMI_E_ARG, "unknown LoRA adapter id " + std::to_string(id));
+    for (int dt : {a_dtype, b_dtype})
+        if (dt != PGMI_DTYPE_BF16 && dt != PGMI_DTYPE_F16 && dt != PGMI_DTYPE_F32) return fail(PGMI_E_ARG, "unsupported dtype");
+    auto it = x->index.find(name);
+    if (it == x->index.end()) return fail(PGMI_E_ARG, std::string("unknown weight ") + name);
+    const Slot& s = x->slots[it->second];
+    if (!lora_targetable(s))
+        return fail(PGMI_E_ARG, std::string(name) + " is not the 2-D weight of a Linear module: not a LoRA target");
+    const int64_t r = a_shape[0];
+    if (r < 1 || r > kLoraMaxRank) return fail(PGMI_E_ARG, std::string(name) + ": LoRA rank " + std::to_string(r) + " outside [1, 256]");
+    if (a_shape[1] != s.shape[1] || b_shape[0] != s.shape[0] || b_shape[1] != r)
+        return fail(PGMI_E_ARG, std::string(name) + ": lora_A must be [r][" + std::to_string(s.shape[1]) + "] and lora_B [" +
+                                    std::to_string(s.shape[0]) + "][r]");
+    if (s.shape[1] % 8 != 0) return fail(PGMI_E_ARG, std::string(name) + ": K must be a multiple of 8");
+    if (lora_find(a, it->second)) return fail(PGMI_E_ARG, std::string(name) + ": the adapter already has this target");
+    if (x->lora_active == id) return fail(PGMI_E_STATE, kLoraActiveMsg);
+    HIPCHK(hipSetDevice(x->device));
+    hipStream_t st = (hipStream_t)stream;
+    LoraTarget t{it->second, (int)r, scaling, nullptr, nullptr};
+    int rc = lora_upload(x, st, A, a_dtype, r * s.shape[1], on_device, &t.A);
+    if (!rc) rc = lora_upload(x, st, B, b_dtype, s.shape[0] * r, on_device, &t.B);
+    if (!rc && on_device && hipStreamSynchronize(st) != hipSuccess) rc = fail(PGMI_E_HIP, "LoRA factor upload");
+    if (rc) {
+        if (t.A) (void)hipFree(t.A);
+        if (t.B) (void)hipFree(t.B);
+        return rc;
+    }
+    a->targets.push_back(t);
+    a->factor_bytes += (r * s.shape[1] + s.shape[0] * r) * (int64_t)sizeof(float);
+    return 0;
+}
+
+int pgmi_lora_active(const pgmi_ctx* x) { return x ? x->lora_active : -1; }
+
+int pgmi_lora_info(const pgmi_ctx* x, int id, int64_t* info, int n) {
+    if (!x || !info) return fail(PGMI_E_ARG, "null argument");
+    const LoraAdapter* a = lora_get(const_cast<pgmi_ctx*>(x), id);
+    if (!a) return fail(PGMI_E_ARG, "unknown LoRA adapter id " + std::to_string(id));
+    if (n < PGMI_LORA_INFO_N) return fail(PGMI_E_ARG, "info needs PGMI_LORA_INFO_N entries");
+    int64_t pristine = 0;
+    for (const LoraTarget& t : a->targets) {
+        auto it = x->lora_pristine.find(t.slot);
+        if (it != x->lora_pristine.end() && it->second.copy) pristine += x->slots[t.slot].numel * 2;
+    }
+    info[0] = (int64_t)a->targets.size(); info[1] = a->factor_bytes; info[2] = pristine;
+    return 0;
+}
+
+// The switch: restore what the outgoing adapter alone had changed, merge the incoming one's targets from their
+// pristine copies, then mark what was derived from a changed tensor.  Everything that can be refused is refused,
+// and every missing copy allocated, before the slab is touched.
+int pgmi_lora_set(pgmi_ctx* x, int id, void* stream) {
+    if (!x) return fail(PGMI_E_ARG, "null argument");
+    LoraAdapter* in = id == -1 ? nullptr : lora_get(x, id);
+    if (id != -1 && !in) return fail(PGMI_E_ARG, "unknown LoRA adapter id " + std::to_string(id));
+    if (!x->slab) return fail(PGMI_E_STATE, "weights are not bound");
+    HIPCHK(hipSetDevice(x->device));
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(PGMI_E_STATE, "pgmi_lora_set inside a stream capture");
+    HIPCHK(hipDeviceSynchronize());
+    if (id == x->lora_active) return 0;
+    const LoraAdapter* out = x->lora_active >= 0 ? &x->lora[x->lora_active] : nullptr;
+    if (in)
+        for (const LoraTarget& t : in->targets) {
+            LoraPristine& p = x->lora_pristine[t.slot];
+            if (p.copy) continue;
+            void* d = nullptr;
+            if (hipMalloc(&d, (size_t)x->slots[t.slot].numel * 2) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(PGMI_E_NOMEM, "pristine copy of " + x->slots[t.slot].name);
+            }
+            p.copy = reinterpret_cast<uint16_t*>(d);
+            p.valid = false;
+        }
+    std::vector<int> changed;
+    if (out)
+        for (const LoraTarget& t : out->targets) {
+            if (lora_find(in, t.slot)) continue;
+            const Slot& sl = x->slots[t.slot];
+            const LoraPristine& p = x->lora_pristine[t.slot];  // valid: it was merged from
+            HIPCHK(hipMemcpyAsync(x->slab + sl.off, p.copy, (size_t)sl.numel * 2, hipMemcpyDeviceToDevice, s));
+            changed.push_back(t.slot);
+        }
+    x->lora_active = -1;  // (until the merges are enqueued: a failure below leaves no adapter claimed)
+    if (in)
+        for (const LoraTarget& t : in->targets) {
+            const Slot& sl = x->slots[t.slot];
+            LoraPristine& p = x->lora_pristine[t.slot];
+            uint16_t* w = reinterpret_cast<uint16_t*>(x->slab + sl.off);
+            if (!p.valid) {  // (never a target of `out`: those copies are valid) the slab holds this tensor's base
+                HIPCHK(hipMemcpyAsync(p.copy, w, (size_t)sl.numel * 2, hipMemcpyDeviceToDevice, s));
+                p.valid = true;
+            }
+            lora_merge(s, p.copy, (int)sl.shape[0], (int)sl.shape[1], t.A, t.B, t.r, t.scaling, w);
+            changed.push_back(t.slot);
+        }
+    LAUNCHCHK();
+    x->lora_active = id;
+    // derived tensors: only what was built from a changed tensor
+    int kinds = 0;
+    for (int slot : changed) {
+        const std::string& nm = x->slots[slot].name;
+        if (nm.compare(0, 28, "language_model.model.layers.") != 0) continue;
+        if (mf_wanted(x->c)) x->mfw_dirty = true;  // rebuilt in place by the next B >= 3 step: its graphs stay valid
+        if (ends_with(nm, "mlp.gate_proj.weight") || ends_with(nm, "mlp.up_proj.weight")) kinds |= PK_GATE_UP;
+        if (ends_with(nm, "mlp.down_proj.weight")) kinds |= PK_DOWN;
+    }
+    if (kinds & x->pk_done) {
+        pk_forget_kinds(x, kinds);
+        drop_small_batch_graphs(x->dgraphs);  // they hold the old images' launches (packed or raw, exponent base)
+        x->pgraphs.clear();                   // (a last-row-only prefill's GEMVs likewise)
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int pgmi_lora_free(pgmi_ctx* x, int id) {
+    if (!x) return fail(PGMI_E_ARG, "null argument");
+    LoraAdapter* a = lora_get(x, id);
+    if (!a) return fail(PGMI_E_ARG, "unknown LoRA adapter id " + std::to_string(id));
+    if (x->lora_active == id) return fail(PGMI_E_STATE, kLoraActiveMsg);
+    if (!a->targets.empty()) {
+        HIPCHK(hipSetDevice(x->device));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    for (LoraTarget& t : a->targets) { (void)hipFree(t.A); (void)hipFree(t.B); }
+    *a = LoraAdapter{};
+    // pristine copies no remaining adapter targets go too
+    for (auto it = x->lora_pristine.begin(); it != x->lora_pristine.end();) {
+        bool wanted = false;
+        for (const LoraAdapter& o : x->lora) wanted = wanted || (o.used && lora_find(&o, it->first));
+        if (wanted) { ++it; continue; }
+        if (it->second.copy) (void)hipFree(it->second.copy);
+        it = x->lora_pristine.erase(it);
+    }
+    return 0;
+}
+
+int pgmi_lora_merge_host(const uint16_t* W, int64_t N, int64_t K, const float* A, const float* B, int r, float scaling,
+                         uint16_t* out) {
+    if (!W || !A || !B || !out) return fail(PGMI_E_ARG, "null argument");
+    if (N < 1 || K < 1) return fail(PGMI_E_ARG, "lora_merge: N, K >= 1");
+    if (r < 1 || r > kLoraMaxRank) return fail(PGMI_E_ARG, "lora_merge: rank outside [1, 256]");
+    for (int64_t n = 0; n < N; ++n)
+        for (int64_t k = 0; k < K; ++k) {
+            float acc = 0.0f;
+            for (int j = 0; j < r; ++j) acc = lora_step(acc, B[n * r + j], A[(int64_t)j * K + k]);
+            out[n * K + k] = lora_finish(W[n * K + k], acc, scaling);
+        }
+    return 0;
+}
+
+int pgmi_op_lora_merge(pgmi_ctx* x, const void* W, int N, int K, const void* A, const void* B, int r, float scaling,
+                       void* out, void* stream) {
+    if (!x || !W || !A || !B || !out) return fail(PGMI_E_ARG, "null argument");
+    if (N < 1 || K < 8 || K % 8 != 0) return fail(PGMI_E_ARG, "lora_merge: N >= 1, K a positive multiple of 8");
+    if (r < 1 || r > kLoraMaxRank) return fail(PGMI_E_ARG, "lora_merge: rank outside [1, 256]");
+    for (const void* p : {W, A, B, (const void*)out})
+        if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return fail(PGMI_E_ARG, "lora_merge: tensors must be 16-byte aligned");
+    HIPCHK(hipSetDevice(x->device));
+    (void)pgmi::launch_error_take(nullptr);
+    lora_merge((hipStream_t)stream, reinterpret_cast<const uint16_t*>(W), N, K, reinterpret_cast<const float*>(A),
+               reinterpret_cast<const float*>(B), r, scaling, reinterpret_cast<uint16_t*>(out));
+    LAUNCHCHK();
+    return 0;
+}
+
 static int decode_step(pgmi_ctx* x, const int64_t* ids, const void* embeds, int B, void* kv, int kv_batch, int kv_max,
                        int kv_len, int position, float* logits, int64_t* next_ids, int use_graph, void* stream,
                        const DevStepIn* dev = nullptr, int n_steps = 1, int64_t* tokens = nullptr,
@@ -1777,6 +2073,7 @@ int pgmi_comm_destroy(void* comm) {
 
 int pgmi_broadcast_weights(pgmi_ctx* x, void* comm, int root, void* stream) {
     if (!x || !comm) return fail(PGMI_E_ARG, "null argument");
+    if (x->lora_active >= 0) return fail(PGMI_E_STATE, kLoraActiveMsg);  // (a merged slab, and copies that do not match)
     if (!x->slab) return fail(PGMI_E_STATE, "weights are not bound (pgmi_bind_weights)");
     RCCL_READY();
     int prev = 0;

@@ -126,6 +126,12 @@ struct PkW {
 // one >= 1 (caller presets 0 / 0xFFFFFFFF); out: pk_image_bytes(rows, K) bytes, K a multiple of 2048
 void pk_scan(hipStream_t s, const uint16_t* W, long numel, unsigned* stat);
 void pk_pack(hipStream_t s, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out);
+// LoRA (kernels_lora.hip, the rule of lora.h): out[N][K] = bf16(W + (B . A) * scaling) from the pristine W (bf16),
+// A[r][K] and B[N][r] in fp32 (all 16-B aligned, K a multiple of 8, r in [1, 256]); out does not overlap W.  lora_widen:
+// n factor values of dtype PGMI_DTYPE_* on the device to fp32.
+void lora_merge(hipStream_t s, const uint16_t* W, int N, int K, const float* A, const float* B, int r, float scaling,
+                uint16_t* out);
+void lora_widen(hipStream_t s, const void* src, int dtype, long n, float* dst);
 // ws: fp32 scratch (>= 4 x B x N floats) for the MFMA path's K split of K = 16384 (B >= 3)
 void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W, int N, uint16_t* h_inout,
               float* ws, PkW pk = {});

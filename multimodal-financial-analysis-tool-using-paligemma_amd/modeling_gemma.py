@@ -514,14 +514,49 @@ class PaliGemmaForConditionalGeneration(nn.Module):
     def pgmi_rebind(self):
         """Forget the engine binding (after replacing Parameter objects): the next forward copies
         the current parameters into a new weight slab (pgmi/binding.py)."""
+        b = self.__dict__.get("_pgmi_bound")
+        if b is not None and b.engine.active_lora is not None:
+            # the parameters are views of the slab the adapter is merged into: put the base back before the next
+            # forward copies them into a new one (which re-activates the adapter, _pgmi_engine)
+            b.engine.set_lora(None)
         _binding.unbind(self)
+
+    def pgmi_load_lora(self, path, name: str) -> None:
+        """Load a peft LoRA checkpoint (a directory with adapter_config.json + adapter_model.safetensors; what the
+        reference's fine-tuning produces) under `name`.  The host factors are kept with the model, so a re-bind (a
+        new engine) loads and re-activates them; nothing is merged until pgmi_set_lora(name)."""
+        from pgmi import lora as _lora
+        held = self.__dict__.setdefault("_pgmi_lora", {})
+        if name is None or name in held:
+            raise ValueError(f"pgmi_load_lora: adapter name {name!r} is " + ("taken" if name is not None else "required"))
+        held[name] = path if isinstance(path, _lora.Adapter) else _lora.read_peft(path)
+
+    def pgmi_set_lora(self, name: Optional[str]) -> None:
+        """Run every following forward under the adapter `name` (None: the base model).  The adapter is merged
+        into the weights on the device (Engine.set_lora): no cost per token; a pending greedy lookahead is
+        dropped with the switch.  While one is active the parameters (views of the weight slab) show the merged
+        values: deactivate before updating weights in place."""
+        if name is not None and name not in self.__dict__.get("_pgmi_lora", {}):
+            raise KeyError(f"pgmi_set_lora: no adapter named {name!r}")
+        self.__dict__["_pgmi_lora_active"] = name
+        if next(self.parameters()).device.type == "cuda":
+            self._pgmi_engine(full_check=True)
 
     def _pgmi_engine(self, full_check: bool = False):
         _check_tied(self.language_model)
         layers = self.language_model.model.layers
-        return _binding.bind(self, lambda: _pgmi_cfg(self.config), "",
-                             inv_freq=layers[0].self_attn.rotary_emb.inv_freq if len(layers) else None,
-                             full_check=full_check)
+        eng = _binding.bind(self, lambda: _pgmi_cfg(self.config), "",
+                            inv_freq=layers[0].self_attn.rotary_emb.inv_freq if len(layers) else None,
+                            full_check=full_check)
+        held = self.__dict__.get("_pgmi_lora")
+        if held:  # adapters were loaded: this engine (a new one after a re-bind) has them and runs the chosen one
+            want = self.__dict__.get("_pgmi_lora_active")
+            if eng.active_lora != want:
+                for name, ad in held.items():
+                    if name not in eng._lora:
+                        eng.load_lora(ad, name)
+                eng.set_lora(want)
+        return eng
 
     def _merge_input_ids_with_image_features(self, image_features: torch.Tensor, inputs_embeds: torch.Tensor,
                                              input_ids: torch.Tensor, attention_mask: torch.Tensor,

@@ -80,6 +80,15 @@ SIGNATURES = {
     "pgmi_pack13_bytes": (i64, [i64, i64]),
     "pgmi_pack13_encode": (i32, [vp, i64, i64, i32, vp]),
     "pgmi_pack13_decode": (i32, [vp, i64, i64, i32, vp]),
+    "pgmi_lora_create": (i32, [vp, ctypes.POINTER(i32)]),
+    "pgmi_lora_add": (i32, [vp, i32, ctypes.c_char_p, vp, i32, ctypes.POINTER(i64), vp, i32, ctypes.POINTER(i64), f32,
+                            i32, vp]),
+    "pgmi_lora_free": (i32, [vp, i32]),
+    "pgmi_lora_set": (i32, [vp, i32, vp]),
+    "pgmi_lora_active": (i32, [vp]),
+    "pgmi_lora_info": (i32, [vp, i32, ctypes.POINTER(i64), i32]),
+    "pgmi_lora_merge_host": (i32, [vp, i64, i64, vp, vp, i32, f32, vp]),
+    "pgmi_op_lora_merge": (i32, [vp, vp, i32, i32, vp, vp, i32, f32, vp, vp]),
     "pgmi_prefill_kernel": (i32, [vp, i32, i32, i32, vp]),
     "pgmi_debug_gemm_tiles": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "pgmi_debug_gemm_plan": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),

@@ -12,6 +12,9 @@ batched decode's fragment-major images, the patch embedding -> its padded copy) 
 not a slab view (its in-place update never reaches the slab).  A change there re-copies those parameters,
 drops the pending greedy lookahead and re-runs prepare() (round-6 verdict: an in-place update of an
 unsampled weight left the derived images and a pending lookahead stale).
+While a LoRA adapter is merged into the slab (Engine.set_lora) the parameters show the merged weights; the library's
+merges and restores touch no version counter, so they never come here, and an update seen while one is active is
+refused (_refuse_update_under_lora): the model deactivates first.
 """
 from __future__ import annotations
 
@@ -86,6 +89,7 @@ class _Bound:
         """An in-place update of a watched parameter: copy what is not a slab view, drop the pending greedy
         lookahead (its logits came from the old weights), rebuild the derived tensors."""
         eng = self.engine
+        _refuse_update_under_lora(eng)
         with torch.no_grad():
             for p, view in self.watch:
                 if p.data_ptr() != view.data_ptr():
@@ -96,6 +100,16 @@ class _Bound:
         eng.prepare(inv_freq=inv_freq)  # synchronises the device: a lookahead still running ends first
         self.wfp = _versions(self.watch)
         self.fp = _fingerprint_of(self.sample)
+
+
+def _refuse_update_under_lora(eng) -> None:
+    """A parameter changed in place (or moved) while a LoRA adapter is merged into the slab the parameters view:
+    the update landed on merged weights, and the pristine copies no longer match any base.  (The library's own
+    merges and restores write the slab without touching torch's version counters, so they never come here.)"""
+    if eng.active_lora is not None:
+        raise RuntimeError(
+            f"a model weight was updated in place while the LoRA adapter {eng.active_lora!r} is active: the parameters "
+            f"hold the merged weights.  Call pgmi_set_lora(None) before changing weights, then re-activate")
 
 
 _warned_dtypes = set()
@@ -125,6 +139,8 @@ def bind(module, cfg: dict, prefix: str, inv_freq=None, full_check: bool = False
         if full_check and _versions(b.watch) != b.wfp:
             b.refresh(inv_freq)
         return b.engine
+    if b is not None:
+        _refuse_update_under_lora(b.engine)
     dev = _device_of(module)
     if callable(cfg):
         cfg = cfg()

@@ -44,6 +44,9 @@ def config_dict(cfg) -> dict:
     }
 
 
+_KEEP = object()  # generate / score: no `adapter` argument -- whatever adapter is active stays
+
+
 class Score(NamedTuple):
     """Engine.score's result: per-token log-probabilities (0 where ignored), each row's sum and live-token count,
     and the reference's loss (modeling_gemma.py:596-603)."""
@@ -92,6 +95,8 @@ class Engine:
         self.prepared = False
         self._logits_buf = {}
         self._gen_buf = {}  # generate(): per-batch-size step buffers
+        self._lora = {}  # LoRA adapters: name -> id in the context (load_lora)
+        self._lora_active = None  # the one merged into the slab now
 
     def __del__(self):
         try:
@@ -112,6 +117,7 @@ class Engine:
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict, strict: bool = True):
+        self._no_lora("load_state_dict")
         missing = [n for n in self.views if n not in sd]
         if strict and missing:
             raise KeyError(f"missing weights: {missing[:5]}{'...' if len(missing) > 5 else ''}")
@@ -129,6 +135,7 @@ class Engine:
         must come from the files.  Returns the number of tensors loaded."""
         import glob
         import os
+        self._no_lora("load_safetensors")
         files = sorted(glob.glob(os.path.join(path, "*.safetensors"))) if os.path.isdir(path) else [path]
         if not files:
             raise FileNotFoundError(f"no *.safetensors under {path}")
@@ -146,8 +153,82 @@ class Engine:
         self.prepared = False
         return total
 
+    # ------------------------------------------------------------------ LoRA adapters
+    def _no_lora(self, what: str) -> None:
+        if self._lora_active is not None:
+            raise RuntimeError(f"{what}: the LoRA adapter {self._lora_active!r} is merged into the weights; "
+                               f"deactivate first (set_lora(None))")
+
+    def load_lora(self, source, name: str) -> None:
+        """Load a LoRA adapter under `name`: a peft directory / adapter_model.safetensors path (pgmi.lora.read_peft),
+        a pgmi.lora.Adapter, or a dict slab weight name -> (A [r][K], B [N][r], scaling).  The factors go to the
+        device as fp32 (pgmi_lora_add); nothing is merged until set_lora(name).  At most 8 adapters per engine."""
+        import numpy as np
+        from . import lora as LR
+        if name is None or name in self._lora:
+            raise ValueError(f"load_lora: adapter name {name!r} is " + ("taken" if name is not None else "required"))
+        if isinstance(source, dict):
+            targets = source
+        elif isinstance(source, LR.Adapter):
+            targets = source.targets
+        else:
+            targets = LR.read_peft(source).targets
+        if not targets:
+            raise ValueError("load_lora: the adapter has no targets")
+        i = ctypes.c_int()
+        N.check(self.lib.pgmi_lora_create(self.ctx, ctypes.byref(i)), "pgmi_lora_create")
+        try:
+            s = N.stream_handle(self.device)
+            for wname, (A, B, scaling) in targets.items():
+                A = np.ascontiguousarray(A.detach().float().cpu().numpy() if torch.is_tensor(A) else A, np.float32)
+                B = np.ascontiguousarray(B.detach().float().cpu().numpy() if torch.is_tensor(B) else B, np.float32)
+                if A.ndim != 2 or B.ndim != 2:
+                    raise ValueError(f"{wname}: LoRA factors are 2-D")
+                N.check(self.lib.pgmi_lora_add(self.ctx, i.value, wname.encode(), A.ctypes.data, N.DTYPE_F32,
+                                               (ctypes.c_int64 * 2)(*A.shape), B.ctypes.data, N.DTYPE_F32,
+                                               (ctypes.c_int64 * 2)(*B.shape), float(np.float32(scaling)), 0, s),
+                        "pgmi_lora_add")
+        except Exception:
+            self.lib.pgmi_lora_free(self.ctx, i.value)
+            raise
+        self._lora[name] = i.value
+
+    def set_lora(self, name: Optional[str]) -> None:
+        """Merge the adapter `name` into the weight slab (None: back to the base model, bit for bit); the adapter
+        active before is taken out first (pgmi_lora_set: synchronises the device).  Every later call -- prefill,
+        decode, replayed graphs -- computes with the merged weights at no extra cost per token."""
+        if name is not None and name not in self._lora:
+            raise KeyError(f"set_lora: no adapter named {name!r} (loaded: {sorted(self._lora)})")
+        if name == self._lora_active:
+            return
+        if self._lora_active is None and not self.prepared:
+            self.prepare()  # the base was written since: the pristine copies are taken from it anew
+        la = self.__dict__.get("_lookahead")
+        if la is not None:  # a pending greedy lookahead's logits came from the outgoing weights
+            la.pending = None
+        N.check(self.lib.pgmi_lora_set(self.ctx, -1 if name is None else self._lora[name], self._s()), "pgmi_lora_set")
+        self._lora_active = name
+
+    @property
+    def active_lora(self) -> Optional[str]:
+        return self._lora_active
+
+    def lora_info(self, name: str) -> dict:
+        """targets, factor_bytes (resident fp32 factors) and pristine_bytes (base copies of its targets held now)."""
+        v = (ctypes.c_int64 * 3)()
+        N.check(self.lib.pgmi_lora_info(self.ctx, self._lora[name], v, 3), "pgmi_lora_info")
+        return {"targets": v[0], "factor_bytes": v[1], "pristine_bytes": v[2]}
+
+    def unload_lora(self, name: str) -> None:
+        """Free an adapter's device memory; the active one must be deactivated first."""
+        if name == self._lora_active:
+            self._no_lora("unload_lora")
+        N.check(self.lib.pgmi_lora_free(self.ctx, self._lora[name]), "pgmi_lora_free")
+        del self._lora[name]
+
     def fill_synthetic(self, seed: int, policy):
         """Device-side deterministic init (oracle/wgen.c recipe); policy(name, shape) -> (scale, offset)."""
+        self._no_lora("fill_synthetic")
         s = N.stream_handle(self.device)
         for n, view in self.views.items():
             scale, offset = policy(n, tuple(view.shape))
@@ -373,15 +454,17 @@ class Engine:
 
     @torch.no_grad()
     def score(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], labels: torch.Tensor,
-              attention_mask: Optional[torch.Tensor] = None, ignore_index: int = -100) -> "Score":
+              attention_mask: Optional[torch.Tensor] = None, ignore_index: int = -100, adapter=_KEEP) -> "Score":
         """The reference's forward(labels=...) loss (modeling_gemma.py:596-603) per token, from one prefill:
         position j is scored against labels[:, j + 1], and only the rows whose shifted label is live go through
         the lm_head (one index_select on the final-normed rows, one host sync; no (B, L, V) tensor exists).
 
         attention_mask (B, L) of 0 / 1: a ragged batch as Engine.generate takes it; ids and labels are moved to
         the right-padded form and pad positions count as ignored whatever their label.  pixel_values None: a
-        text-only prompt.  Returns Score(logprobs (B, L - 1) fp32 with 0 where ignored, sums (B,), counts (B,),
-        loss = -mean over the live tokens, NaN when there is none)."""
+        text-only prompt.  adapter: as generate's.  Returns Score(logprobs (B, L - 1) fp32 with 0 where ignored,
+        sums (B,), counts (B,), loss = -mean over the live tokens, NaN when there is none)."""
+        if adapter is not _KEEP:
+            self.set_lora(adapter)
         ids = input_ids.to(self.device, torch.int64)
         lab = labels.to(self.device, torch.int64)
         if tuple(lab.shape) != tuple(ids.shape):
@@ -593,7 +676,7 @@ class Engine:
                  kv: torch.Tensor = None, do_sample: bool = False, temperature: float = 0.8, top_p: float = 0.9,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, sync_every: int = 16, return_lengths: bool = False,
-                 attention_mask: Optional[torch.Tensor] = None, return_logprobs: bool = False):
+                 attention_mask: Optional[torch.Tensor] = None, return_logprobs: bool = False, adapter=_KEEP):
         """Batched generation: prefill, then n_tokens-1 decode steps
         with the next token picked on the device -- greedy argmax, or with do_sample the
         temperature + top-p draw of inference.py:64-66 -- and no host sync per token.
@@ -616,7 +699,12 @@ class Engine:
         return_logprobs: also return fp32 (B, n_tokens) (last in the returned tuple): the log-probability of each
         emitted token under softmax of the raw step logits (pgmi_logprobs) -- no temperature and no top-p
         renormalisation, whatever the sampling settings -- and 0 for the pad emitted after a row's eos.  The
-        loop then runs one launch per step, as do_sample does; the tokens are the same."""
+        loop then runs one launch per step, as do_sample does; the tokens are the same.
+
+        adapter: the name of a loaded LoRA adapter to generate under, or None for the base model; the engine
+        switches first when it is not the active one (set_lora).  Left out: whatever is active stays."""
+        if adapter is not _KEEP:
+            self.set_lora(adapter)
         ids = input_ids.to(self.device, torch.int64)
         lens = R.lengths_from_mask(attention_mask) if attention_mask is not None else None
         if lens is not None:
