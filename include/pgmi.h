@@ -344,8 +344,34 @@ int pgmi_decode_kernel(pgmi_ctx* ctx, int which, int layer, int B, void* stream)
 /* Test hook: copy `bytes` bytes between the decode workspace pgmi_decode_kernel works on and the caller's device
  * memory `buf` (write != 0: buf -> workspace): which 0 = h (bf16 [max_batch][hidden], kernel 2's input, kernel 1's
  * and 3's in/out), 1 = act (bf16 [max_batch][intermediate], kernel 2's output, 3's input), 2 = kernel 4's logits
- * (fp32 [max_batch][vocab]).  Stream-ordered.  PGMI_E_ARG: a byte count outside the buffer. */
+ * (fp32 [max_batch][vocab]; stage 5's too).  The buffers pgmi_debug_decode_stage works on besides: 3 = q (bf16
+ * [max_batch][heads * head_dim]), 4 = the combined attention output (bf16 [max_batch][hidden]; written at B >= 3
+ * only -- at B <= 2 the combine stays in o_proj's registers), 5 = hn, the normed rows the unstaged B >= 3 q|k|v
+ * reads (bf16 [max_batch][hidden]), 6 = ssq, o_proj's 16-column partial sums of squares of h (fp32
+ * [max_batch][hidden / 16], unstaged B >= 3 only), 7 = the step's next-id buffer (int64 [max_batch]).
+ * Stream-ordered.  PGMI_E_ARG: a byte count outside the buffer. */
 int pgmi_debug_decode_buffer(pgmi_ctx* ctx, int which, void* buf, int64_t bytes, int write, void* stream);
+/* Test hook: run ONE stage of the decode step for batch B through the step's own launch code (the functions
+ * pgmi_decode's body calls, with the same arguments), at the current pgmi_set_decode_staged_norm /
+ * pgmi_set_decode_packed settings, on the decode workspace (pgmi_debug_decode_buffer):
+ *   0  the step's entry (layer == 0; other layers: nothing).  B <= 2 with ids: nothing (layer 0's q|k|v folds the
+ *      embedding).  B >= 3: embedding x bf16(sqrt(hidden)) -> h, then (unstaged form) layer 0's input norm -> hn.
+ *      ids == NULL: h is what the caller wrote into the workspace.             ids / h -> h, hn
+ *   1  q|k|v: input norm (or the hn read), projection, RoPE, KV append          h / hn  -> q, KV rows
+ *   2  attention partials + combine + o_proj + residual                         q, KV   -> h (B >= 3: ao, ssq)
+ *   3  post-attention norm + gate|up + GeGLU                                    h, ssq  -> act
+ *   4  down + residual (unstaged B >= 3: + the next layer's input norm -> hn)    act, h  -> h, hn
+ *   5  final norm + lm_head + argmax (layer ignored)                            h -> logits (buffer 2), next ids (7)
+ * ids: device int64 [B] or NULL (stages 0 and 1 of layer 0 read it).  kv / kv_batch / kv_max: as pgmi_decode.
+ * kv_lens / positions: HOST arrays; ragged == 0 reads element 0 of each into the lock-step record, ragged != 0
+ * sets one record per row (B entries), as pgmi_decode_ragged.  Every call sets the record(s) it uses, and sets
+ * them again after stage 5, whose last kernel advances them.  mask (device, may be NULL; B == 1 only): kv_lens[0]
+ * + 1 additive values of mask_dtype bf16 / fp32, the mask of pgmi_decode_embeds_dev.  Eager only: PGMI_E_STATE
+ * inside a stream capture.  PGMI_E_ARG: an unknown stage, a layer out of range (stages 1..4), B over capacity,
+ * kv_lens[b] + 1 > kv_max, a mask with B != 1. */
+int pgmi_debug_decode_stage(pgmi_ctx* ctx, int stage, int layer, int B, const int64_t* ids, void* kv, int kv_batch,
+                            int kv_max, const int32_t* kv_lens, const int32_t* positions, int ragged, const void* mask,
+                            int mask_dtype, void* stream);
 
 /* Image preprocessing on the GPU (processing_paligemma.py:13-49, process_images): PIL-exact
  * BICUBIC resize of one decoded RGB image (uint8 HWC, device memory, H x W) to out_h x out_w,

@@ -1204,73 +1204,122 @@ static int lm_rows(pgmi_ctx* x, hipStream_t s, int b0, int B, int L, void* kv, i
 // (kernels_gemv_mfma.hip PGMI_MF_NT) the unstaged form wins, same box: 1.4523 / 1.4550 -> 1.4330 / 1.4320 ms
 static bool mf_staged(const pgmi_ctx* x) { return x->mf_staged > 0; }
 
-static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, void* kv, int kv_batch, int kv_max,
-                       int launch_keys, float* logits, int64_t* next_ids, const uint16_t* embeds = nullptr,
-                       int masked = 0, int64_t* hist = nullptr, bool ragged = false) {
+// One decode step's launches, shared by decode_body and the stage hook (pgmi_debug_decode_stage): what the
+// head, each layer and the tail read besides the context.
+struct DecodeRun {
+    hipStream_t s;
+    const int64_t* ids;      // token ids (null: h is given -- embeds, or the hook's caller wrote dH)
+    const uint16_t* embeds;  // given input rows (pgmi_decode_embeds), else null
+    int B;
+    void* kv;
+    int kv_batch, kv_max;
+    int launch_keys;         // upper bound on kv_len + 1 (sizes the attention grid)
+    int masked;              // 0: no mask, 1: staged bf16 mask, 2: staged fp32 mask
+    bool ragged;             // one step record per row (x->rstep), else x->step
+};
+
+static StepState* run_step(const pgmi_ctx* x, const DecodeRun& r) { return r.ragged ? x->rstep : x->step; }
+// B <= 2: the embedding row is read by layer 0's q|k|v GEMV itself (one launch fewer per step)
+static bool run_folds(const pgmi_ctx* x, const DecodeRun& r) {
+    return !r.embeds && r.ids && gemv_qkv_folds_embed(r.B) && x->c.t_layers > 0;
+}
+// B >= 3 (MFMA projections): every RMSNorm is computed once per row -- the input norm fused into the
+// down projection's combine for the next layer (q|k|v reads dHn unstaged), the post-attention norm's
+// sums of squares written by o_proj's epilogue (dSS) and applied by gate|up as it loads h.  (Round 5,
+// the input norm the same way -- the down combine writing partials, q|k|v normalising on load: q|k|v
+// 5.97 -> 7.59 us for a combine no shorter, 4.63 -> 4.72 us; with the combine inside the down launch,
+// B = 8 step 1.437 -> 1.446-1.465 ms, same box.)
+static bool run_mf(const pgmi_ctx* x, const DecodeRun& r) { return r.B >= gemv_mf_min_batch() && !mf_staged(x); }
+static float embed_normalizer(const pgmi_ctx* x) { return bf16_round_host(std::sqrt((float)x->c.t_hidden)); }
+
+// the step's entry: h (unless layer 0's q|k|v folds the embedding) and, unstaged, layer 0's normed rows
+static void decode_head(pgmi_ctx* x, const DecodeRun& r) {
     const pgmi_config& c = x->c;
-    // the step record(s) the kernels read: one shared by every row, or (ragged) one per row
-    StepState* const st = ragged ? x->rstep : x->step;
-    const int sts = ragged ? 1 : 0, adv_n = ragged ? B : 1;
+    const int H = c.t_hidden;
+    // given input rows (a caller's merge, pgmi_decode_embeds): h = rows x bf16(sqrt(hidden)) (modeling_gemma.py:367-368)
+    if (r.embeds) scale_rows(r.s, r.embeds, (long)r.B * H, embed_normalizer(x), x->dH);
+    else if (r.ids && !run_folds(x, r))
+        embed_rows(r.s, r.ids, r.B, x->w.embed, H, embed_normalizer(x), c.pad_token_id, x->dH);
+    if (run_mf(x, r) && c.t_layers > 0) rows_norm(r.s, x->dH, x->w.t[0].in_norm, c.t_rms_eps, r.B, H, x->dHn);
+}
+
+// layer i's launches; stage 0: all of them, 1..4: that one alone (1 q|k|v, 2 attention + o_proj,
+// 3 gate|up, 4 down -- the stage numbers of pgmi_debug_decode_stage)
+static void decode_layer(pgmi_ctx* x, const DecodeRun& r, int i, int stage = 0) {
+    const pgmi_config& c = x->c;
+    hipStream_t s = r.s;
+    const int B = r.B;
+    StepState* const st = run_step(x, r);
+    const int sts = r.ragged ? 1 : 0;
     const int H = c.t_hidden, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
     const float eps = c.t_rms_eps;
-    const float normalizer = bf16_round_host(std::sqrt((float)H));
-    const uint16_t* E = x->w.embed;
-    const long kvd = (long)NKV * HD, kvb = (long)kv_max * kvd;
-    uint16_t* kvp = reinterpret_cast<uint16_t*>(kv);
-    // B <= 2: the embedding row is read by layer 0's q|k|v GEMV itself (one launch fewer per step)
-    const bool fold = !embeds && gemv_qkv_folds_embed(B) && c.t_layers > 0;
-    const EmbedFold emb{ids, E, normalizer, c.pad_token_id, x->dH};
-    // given input rows (a caller's merge, pgmi_decode_embeds): h = rows x bf16(sqrt(hidden)) (modeling_gemma.py:367-368)
-    if (embeds) scale_rows(s, embeds, (long)B * H, normalizer, x->dH);
-    else if (!fold) embed_rows(s, ids, B, E, H, normalizer, c.pad_token_id, x->dH);
-    // B >= 3 (MFMA projections): every RMSNorm is computed once per row -- the input norm fused into the
-    // down projection's combine for the next layer (q|k|v reads dHn unstaged), the post-attention norm's
-    // sums of squares written by o_proj's epilogue (dSS) and applied by gate|up as it loads h.  (Round 5,
-    // the input norm the same way -- the down combine writing partials, q|k|v normalising on load: q|k|v
-    // 5.97 -> 7.59 us for a combine no shorter, 4.63 -> 4.72 us; with the combine inside the down launch,
-    // B = 8 step 1.437 -> 1.446-1.465 ms, same box.)
-    const bool mf = B >= gemv_mf_min_batch() && !mf_staged(x);
-    if (mf && c.t_layers > 0) rows_norm(s, x->dH, x->w.t[0].in_norm, eps, B, H, x->dHn);
-    for (int i = 0; i < c.t_layers; ++i) {
-        uint16_t* Kc = kvp + ((long)(i * 2 + 0) * kv_batch) * kvb;
-        uint16_t* Vc = kvp + ((long)(i * 2 + 1) * kv_batch) * kvb;
-        // w.mf_*: the fragment-major images of this layer's weights (ensure_mf_image), null until built
-        const TextLayerW& w = x->w.t[i];
+    const long kvd = (long)NKV * HD, kvb = (long)r.kv_max * kvd;
+    uint16_t* kvp = reinterpret_cast<uint16_t*>(r.kv);
+    const bool mf = run_mf(x, r);
+    const auto on = [stage](int k) { return stage == 0 || stage == k; };
+    uint16_t* Kc = kvp + ((long)(i * 2 + 0) * r.kv_batch) * kvb;
+    uint16_t* Vc = kvp + ((long)(i * 2 + 1) * r.kv_batch) * kvb;
+    // w.mf_*: the fragment-major images of this layer's weights (ensure_mf_image), null until built
+    const TextLayerW& w = x->w.t[i];
+    if (on(1)) {
+        const EmbedFold emb{r.ids, x->w.embed, embed_normalizer(x), c.pad_token_id, x->dH};
         gemv_qkv(s, B, NH, NKV, mf ? x->dHn : x->dH, mf ? nullptr : w.in_norm, eps, w.qkv, x->cosT, x->sinT,
-                 c.t_max_pos, st, x->dQ, Kc, Vc, kvb, x->ws, (fold && i == 0) ? &emb : nullptr, w.mf_qkv, sts);
+                 c.t_max_pos, st, x->dQ, Kc, Vc, kvb, x->ws, (run_folds(x, r) && i == 0) ? &emb : nullptr, w.mf_qkv,
+                 sts);
+    }
+    if (on(2)) {
         AttnArgs a{};
         a.q = x->dQ; a.q_b_stride = (long)NH * HD; a.q_row_stride = NH * HD; a.q_head_stride = HD;
         a.k = Kc; a.k_b_stride = kvb; a.k_row_stride = (int)kvd; a.k_head_stride = HD;
         a.v = Vc; a.v_b_stride = kvb; a.v_row_stride = (int)kvd; a.v_head_stride = HD;
         a.o = x->dAO; a.o_b_stride = (long)H; a.o_row_stride = H; a.o_head_stride = HD;
         a.Lq = 1; a.Lk = 0; a.G = NH / NKV; a.n_kv = NKV; a.B = B; a.scale = 1.0f / std::sqrt((float)HD);
-        if (masked) {  // the staged additive mask (pgmi_decode_embeds_dev), row stride max_kv
-            a.mask = x->d_mask; a.mask_b_stride = c.max_kv; a.mask_k_stride = 1; a.mask_round = masked == 1;
+        if (r.masked) {  // the staged additive mask (pgmi_decode_embeds_dev), row stride max_kv
+            a.mask = x->d_mask; a.mask_b_stride = c.max_kv; a.mask_k_stride = 1; a.mask_round = r.masked == 1;
         } else {
             a.mask = x->d_zero; a.mask_b_stride = 0; a.mask_k_stride = 0; a.mask_round = 1;
         }
-        attention_decode(s, a, st, launch_keys, x->opart, x->max_chunks, sts);
+        attention_decode(s, a, st, r.launch_keys, x->opart, x->max_chunks, sts);
         gemv_o_attn(s, B, NH, x->opart, x->max_chunks, st, w.o, H, x->dH, B >= gemv_mf_min_batch() ? x->dAO : nullptr,
                     mf ? x->dSS : nullptr, w.mf_o, sts);
-        if (mf) {
-            // the post-attention RMSNorm: its sums of squares come from o_proj's epilogue (dSS), gate|up
-            // normalises h on load (no k_rows_norm pass: B = 8 step -5 us per layer)
+    }
+    if (mf) {
+        // the post-attention RMSNorm: its sums of squares come from o_proj's epilogue (dSS), gate|up
+        // normalises h on load (no k_rows_norm pass: B = 8 step -5 us per layer)
+        if (on(3))
             gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, x->dSS, w.mf_gate_up);
+        if (on(4))
             gemv_res_norm(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws,
                           i + 1 < c.t_layers ? x->w.t[i + 1].in_norm : nullptr, eps, x->dHn, w.mf_down);
-            continue;
-        }
+        return;
+    }
+    if (on(3))
         gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
                    pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
+    if (on(4))
         gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws, pk_use(x, B, PK_DOWN, w.pk_down));
-    }
+}
+
+// final norm + lm_head + argmax.  The step's last work also advances the device step state (pgmi_decode
+// skips its host-side set when the next call continues the sequence): lm_head's last workgroup, or argmax_finish
+static void decode_tail(pgmi_ctx* x, const DecodeRun& r, float* logits, int64_t* next_ids, int64_t* hist) {
+    const pgmi_config& c = x->c;
+    StepState* const st = run_step(x, r);
+    const int adv_n = r.ragged ? r.B : 1;
     int nparts = 0;
     int64_t* nx = next_ids ? next_ids : x->d_next;
-    // the step's last work also advances the device step state (pgmi_decode skips its host-side
-    // set when the next call continues the sequence): lm_head's last workgroup, or argmax_finish
-    if (!gemv_logits(s, B, x->dH, x->w.final_norm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts, x->lm_done, nx,
-                     st, hist, adv_n, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed)))
-        argmax_finish(s, B, x->pmax, x->pidx, nparts, nx, st, hist, adv_n);
+    if (!gemv_logits(r.s, r.B, x->dH, x->w.final_norm, c.t_rms_eps, x->w.embed, c.t_vocab, logits, x->pmax, x->pidx,
+                     &nparts, x->lm_done, nx, st, hist, adv_n, pk_use(x, r.B, PK_LM_HEAD, x->w.pk_embed)))
+        argmax_finish(r.s, r.B, x->pmax, x->pidx, nparts, nx, st, hist, adv_n);
+}
+
+static int decode_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, int B, void* kv, int kv_batch, int kv_max,
+                       int launch_keys, float* logits, int64_t* next_ids, const uint16_t* embeds = nullptr,
+                       int masked = 0, int64_t* hist = nullptr, bool ragged = false) {
+    const DecodeRun r{s, ids, embeds, B, kv, kv_batch, kv_max, launch_keys, masked, ragged};
+    decode_head(x, r);
+    for (int i = 0; i < x->c.t_layers; ++i) decode_layer(x, r, i);
+    decode_tail(x, r, logits, next_ids, hist);
     return launcher_error();  // (inside a capture too: a step with a launch missing is never instantiated)
 }
 
@@ -2139,6 +2188,66 @@ int pgmi_decode_kernel(pgmi_ctx* x, int which, int layer, int B, void* stream) {
     return 0;
 }
 
+int pgmi_debug_decode_stage(pgmi_ctx* x, int stage, int layer, int B, const int64_t* ids, void* kv, int kv_batch,
+                            int kv_max, const int32_t* kv_lens, const int32_t* positions, int ragged, const void* mask,
+                            int mask_dtype, void* stream) {
+    int rc;
+    if (!x || !kv || !kv_lens || !positions) return fail(PGMI_E_ARG, "null argument");
+    if ((rc = ensure_prepared(x))) return rc;
+    const pgmi_config& c = x->c;
+    if (stage < 0 || stage > 5)
+        return fail(PGMI_E_ARG, "decode stage: 0 entry, 1 q|k|v, 2 attention + o_proj, 3 gate|up, 4 down, 5 lm_head");
+    if (B < 1 || B > c.max_batch || B > kv_batch || B > kMaxRows) return fail(PGMI_E_ARG, "batch exceeds capacity");
+    if (stage >= 1 && stage <= 4 && (layer < 0 || layer >= c.t_layers)) return fail(PGMI_E_ARG, "layer out of range");
+    if (kv_max > c.max_kv) return fail(PGMI_E_ARG, "kv_max exceeds config max_kv");
+    if (mask && B != 1) return fail(PGMI_E_ARG, "a mask: one sequence per step (B = 1)");
+    if (mask && mask_dtype != PGMI_DTYPE_BF16 && mask_dtype != PGMI_DTYPE_F32)
+        return fail(PGMI_E_ARG, "mask dtype must be bf16 or fp32");
+    const int rows = ragged ? B : 1;
+    int kv_len = 0;
+    for (int b = 0; b < rows; ++b) {
+        if (kv_lens[b] < 0 || (long)kv_lens[b] + 1 > kv_max)
+            return fail(PGMI_E_ARG, "KV cache capacity exceeded (kv_lens[b] + 1 > kv_max)");
+        kv_len = std::max(kv_len, (int)kv_lens[b]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(PGMI_E_STATE, "pgmi_debug_decode_stage inside a stream capture");
+    if (B >= gemv_mf_min_batch() && (rc = ensure_mf_image(x, s))) return rc;
+    if (B < gemv_mf_min_batch() && (rc = ensure_pk_image(x, s, B))) return rc;
+    // the step record(s) are set by every call (and so restored after stage 5, whose last kernel advances
+    // them); the decode entry points set theirs again afterwards
+    const auto set_records = [&]() {
+        if (ragged) {
+            RowInts rk{}, rp{};
+            for (int b = 0; b < B; ++b) { rk.v[b] = kv_lens[b]; rp.v[b] = positions[b]; }
+            set_step_rows(s, x->rstep, rk, rp, B);
+            x->rstep_known = false;
+        } else {
+            set_step(s, x->step, kv_lens[0], positions[0]);
+            x->step_known = false;
+        }
+    };
+    set_records();
+    int masked = 0;
+    if (mask) {
+        stage_mask(s, mask, mask_dtype, B, kv_len + 1, kv_len + 1, x->d_mask, c.max_kv);
+        masked = mask_dtype == PGMI_DTYPE_F32 ? 2 : 1;
+    }
+    const DecodeRun r{s, ids, nullptr, B, kv, kv_batch, kv_max, kv_len + 1, masked, ragged != 0};
+    if (stage == 0) {
+        if (layer == 0) decode_head(x, r);
+    } else if (stage <= 4) {
+        decode_layer(x, r, layer, stage);
+    } else {
+        decode_tail(x, r, x->dlogits, nullptr, nullptr);
+        set_records();
+    }
+    LAUNCHCHK();
+    return 0;
+}
+
 int pgmi_debug_decode_buffer(pgmi_ctx* x, int which, void* buf, int64_t bytes, int write, void* stream) {
     int rc;
     if (!x || !buf) return fail(PGMI_E_ARG, "null argument");
@@ -2150,7 +2259,12 @@ int pgmi_debug_decode_buffer(pgmi_ctx* x, int which, void* buf, int64_t bytes, i
         case 0: p = x->dH; cap = (int64_t)c.max_batch * c.t_hidden * 2; break;
         case 1: p = x->dACT; cap = (int64_t)c.max_batch * c.t_intermediate * 2; break;
         case 2: p = x->dlogits; cap = (int64_t)c.max_batch * c.t_vocab * 4; break;
-        default: return fail(PGMI_E_ARG, "decode buffer: 0 h, 1 act, 2 logits");
+        case 3: p = x->dQ; cap = (int64_t)c.max_batch * c.t_heads * c.t_head_dim * 2; break;
+        case 4: p = x->dAO; cap = (int64_t)c.max_batch * c.t_hidden * 2; break;
+        case 5: p = x->dHn; cap = (int64_t)c.max_batch * c.t_hidden * 2; break;
+        case 6: p = x->dSS; cap = (int64_t)c.max_batch * (c.t_hidden / 16) * 4; break;
+        case 7: p = x->d_next; cap = (int64_t)c.max_batch * 8; break;
+        default: return fail(PGMI_E_ARG, "decode buffer: 0 h, 1 act, 2 logits, 3 q, 4 ao, 5 hn, 6 ssq, 7 next ids");
     }
     if (bytes < 1 || bytes > cap) return fail(PGMI_E_ARG, "decode buffer: byte count outside the buffer");
     HIPCHK(hipMemcpyAsync(write ? p : buf, write ? buf : p, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));

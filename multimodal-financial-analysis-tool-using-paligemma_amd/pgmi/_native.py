@@ -108,6 +108,7 @@ SIGNATURES = {
     "pgmi_eos_update": (i32, [vp, vp, vp, i32, i64, i64, vp, vp]),
     "pgmi_decode_kernel": (i32, [vp, i32, i32, i32, vp]),
     "pgmi_debug_decode_buffer": (i32, [vp, i32, vp, i64, i32, vp]),
+    "pgmi_debug_decode_stage": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp]),
     "pgmi_tune_gemm": (i32, [i32, i32]),
     "pgmi_tune_gemm_shape": (i32, [i32, i32, i32, i32, i32, i32]),
     "pgmi_tune_attention": (i32, [i32]),

@@ -633,9 +633,37 @@ class Engine:
         self._ready()
         N.check(self.lib.pgmi_decode_kernel(self.ctx, int(which), int(layer), int(B), self._s()), "pgmi_decode_kernel")
 
+    def decode_stage(self, stage: int, layer: int, B: int, kv: torch.Tensor, kv_lens, positions, ids: torch.Tensor = None,
+                     ragged: bool = False, mask: torch.Tensor = None) -> None:
+        """One stage of the decode step through the step's own launch code (pgmi_debug_decode_stage: a test hook):
+        0 entry, 1 q|k|v, 2 attention + o_proj, 3 gate|up, 4 down, 5 lm_head, on the workspace decode_buffer
+        reads and writes.  kv_lens / positions: an int (lock-step) or B host ints (ragged, or lock-step, which
+        reads the first).  mask (B = 1): kv_lens + 1 additive values, bf16 or fp32, on the device."""
+        self._ready()
+        kl = torch.as_tensor(kv_lens).detach().to("cpu", torch.int32).reshape(-1).contiguous()
+        ps = torch.as_tensor(positions).detach().to("cpu", torch.int32).reshape(-1).contiguous()
+        if kl.numel() < (B if ragged else 1) or ps.numel() < (B if ragged else 1):
+            raise ValueError("decode_stage: kv_lens / positions need one entry (lock-step) or B (ragged)")
+        if ids is not None:
+            if ids.dtype is not torch.int64 or ids.device != self.device or not ids.is_contiguous() or ids.numel() < B:
+                raise ValueError("decode_stage: ids must be a contiguous int64 tensor of B entries on the device")
+        mdt = N.DTYPE_BF16
+        if mask is not None:
+            if mask.device != self.device or not mask.is_contiguous() or mask.dtype not in (torch.bfloat16,
+                                                                                            torch.float32):
+                raise ValueError("decode_stage: mask must be a contiguous bf16 / fp32 tensor on the device")
+            if mask.numel() != int(kl[0]) + 1:
+                raise ValueError(f"mask has {mask.numel()} keys, the step attends {int(kl[0]) + 1}")
+            mdt = N.DTYPE_F32 if mask.dtype == torch.float32 else N.DTYPE_BF16
+        N.check(self.lib.pgmi_debug_decode_stage(self.ctx, int(stage), int(layer), int(B), N.ptr(ids), kv.data_ptr(),
+                                                 kv.shape[2], kv.shape[3], kl.data_ptr(), ps.data_ptr(),
+                                                 int(bool(ragged)), N.ptr(mask), mdt, self._s()),
+                "pgmi_debug_decode_stage")
+
     def decode_buffer(self, which: int, t: torch.Tensor, write: bool = False) -> torch.Tensor:
-        """Copy the decode workspace's h (0) / act (1) / logits (2) rows into the contiguous device tensor t, or
-        (write) t into the workspace (pgmi_debug_decode_buffer: a test hook)."""
+        """Copy the decode workspace's h (0) / act (1) / logits (2) / q (3) / attention output (4, B >= 3) / hn (5) /
+        ssq (6) / next ids (7) rows into the contiguous device tensor t, or (write) t into the workspace
+        (pgmi_debug_decode_buffer: a test hook)."""
         self._ready()
         if t.device != self.device or not t.is_contiguous():
             raise ValueError("decode_buffer: a contiguous tensor on the engine's device")
