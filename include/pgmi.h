@@ -435,6 +435,38 @@ int pgmi_tune_attention(int variant);
 int pgmi_sample_top_p(pgmi_ctx* ctx, const float* x, int rows, int V, float temperature, float top_p,
                       const float* u, int64_t* out, float* kept_mass, void* stream);
 
+/* Logit processors between a step's logits and the pick (pgmi_argmax / pgmi_sample_top_p): the rule only so far,
+ * on host arrays; the device kernels and generate's use of them are left out.  The reference's
+ * loop (inference.py:57-71) has none of them; each restates a published rule, and csrc/logits_rule.h states all
+ * of them once, in a header that compiles for the host and for the device:
+ *   rp   transformers' RepetitionPenaltyLogitsProcessor over prompt and output: x < 0 ? x * rp : x / rp
+ *   fp, pp  the OpenAI / vLLM frequency and presence penalties over emitted tokens: x - fp * n_out, x - pp
+ *   bias  a dense fp32 [V] row added to every row (transformers' SequenceBiasLogitsProcessor for single tokens;
+ *         -inf bans); the caller refuses +inf and NaN entries
+ *   suppress_id, min_new_tokens  transformers' MinNewTokensLengthLogitsProcessor: x[suppress_id] = -inf while
+ *         emitted[row] < min_new_tokens (suppress_id < 0 or min_new_tokens <= 0: off)
+ *   top_k  transformers' TopKLogitsWarper, by value (ties at the k-th value all stay); 0 or >= V: off
+ *   min_p_delta  transformers' MinPLogitsWarper decided in logit space: keep y >= max(y) + delta with
+ *         delta = fp32(T * ln(min_p)) <= 0 from the host; -inf: off
+ * in that order; the two thresholds are one, max(kth, max + delta).  A row the first four leave without a finite
+ * maximum comes back as the raw x (pgmi_argmax has no index for such a row).  A neutral parameter's step is
+ * skipped, so all-neutral parameters copy x bit for bit. */
+typedef struct pgmi_logits_params {
+    float rp, pp, fp;
+    int top_k;
+    float min_p_delta;
+    int suppress_id;
+    int min_new_tokens;
+} pgmi_logits_params;
+/* y (fp32 [rows][V], y == x allowed) = the rule applied to x, all host arrays; the k-th value by a sort.  No
+ * context, no GPU.  history: uint32 [rows][V], word v = (v occurs in the row's prompt) << 31 | times the row has
+ * emitted v; NULL allowed when rp == 1 and pp == fp == 0.  bias (fp32 [V]) may be NULL; emitted (int32 [rows],
+ * tokens each row has emitted so far) may be NULL when the suppress is off.  PGMI_E_ARG: rp <= 0 or a non-finite
+ * penalty, top_k < 0, min_p_delta > 0 or NaN, a penalty without a history, a suppress without emitted or with
+ * suppress_id >= V, rows or V <= 0. */
+int pgmi_logits_process_host(const float* x, int rows, int V, const uint32_t* history, const float* bias,
+                             const pgmi_logits_params* params, const int32_t* emitted, float* y);
+
 /* ---- single-op entry points (kernel-level parity tests) ---------------------------------- */
 /* out = epilogue(A[M,K] . W[N,K]^T): epi 0 store, 1 +bias, 2 +bias,gelu, 3 +bias,+res, 4 +res,
  * 6 fp32 out (out is float*), 7 GeGLU with up rows at W + N*K */

@@ -22,6 +22,7 @@
 #include "../../include/pgmi.h"
 #include "common.h"
 #include "launch.h"
+#include "logits_rule.h"
 #include "lora.h"
 #include "pack13.h"
 #include "safetensors_hdr.h"
@@ -2361,6 +2362,66 @@ int pgmi_sample_top_p(pgmi_ctx* x, const float* logits, int rows, int V, float t
                      out + r0, kept_mass ? kept_mass + r0 : nullptr);
     }
     LAUNCHCHK();
+    return 0;
+}
+
+// pgmi_logits_params -> the rule's own record, with what the ABI refuses
+static int logits_rule_from(const pgmi_logits_params* p, int rows, int V, const uint32_t* history,
+                            const int32_t* emitted, LogitsRule* R) {
+    if (!p) return fail(PGMI_E_ARG, "null argument");
+    if (rows <= 0 || V <= 0) return fail(PGMI_E_ARG, "logits_process: empty logits");
+    if (!std::isfinite(p->rp) || !(p->rp > 0.f)) return fail(PGMI_E_ARG, "logits_process: rp must be finite and > 0");
+    if (!std::isfinite(p->pp) || !std::isfinite(p->fp))
+        return fail(PGMI_E_ARG, "logits_process: pp and fp must be finite");
+    if (p->top_k < 0) return fail(PGMI_E_ARG, "logits_process: top_k must be >= 0");
+    if (!(p->min_p_delta <= 0.f)) return fail(PGMI_E_ARG, "logits_process: min_p_delta must be <= 0 (-inf: off)");
+    R->rp = p->rp; R->pp = p->pp; R->fp = p->fp;
+    R->use_rp = p->rp != 1.f;
+    R->use_pp = p->pp != 0.f;
+    R->use_fp = p->fp != 0.f;
+    if ((R->use_rp || R->use_pp || R->use_fp) && !history)
+        return fail(PGMI_E_ARG, "logits_process: a penalty needs the token history");
+    const bool sup = p->suppress_id >= 0 && p->min_new_tokens > 0;
+    if (sup && p->suppress_id >= V) return fail(PGMI_E_ARG, "logits_process: suppress_id outside the vocabulary");
+    if (sup && !emitted) return fail(PGMI_E_ARG, "logits_process: the suppress needs the emitted counts");
+    R->suppress_id = sup ? p->suppress_id : -1;
+    R->min_new_tokens = sup ? p->min_new_tokens : 0;
+    R->top_k = p->top_k >= V ? 0 : p->top_k;
+    R->delta = p->min_p_delta;
+    return 0;
+}
+
+int pgmi_logits_process_host(const float* logits, int rows, int V, const uint32_t* history, const float* bias,
+                             const pgmi_logits_params* params, const int32_t* emitted, float* y) {
+    if (!logits || !y) return fail(PGMI_E_ARG, "null argument");
+    LogitsRule R;
+    if (int rc = logits_rule_from(params, rows, V, history, emitted, &R)) return rc;
+    std::vector<float> y1((size_t)V), sorted;
+    for (int r = 0; r < rows; ++r) {
+        const float* xr = logits + (size_t)r * V;
+        const uint32_t* hr = history ? history + (size_t)r * V : nullptr;
+        float* yr = y + (size_t)r * V;
+        const bool sup = R.suppress_id >= 0 && emitted[r] < R.min_new_tokens;
+        float m = lgr_neg_inf();
+        for (int v = 0; v < V; ++v) {
+            float e = lgr_stage1(xr[v], hr ? hr[v] : 0u, R, bias != nullptr, bias ? bias[v] : 0.f);
+            if (sup && v == R.suppress_id) e = lgr_neg_inf();
+            y1[v] = e;
+            if (e > m) m = e;
+        }
+        if (m == lgr_neg_inf()) {  // the guard: everything banned -> the raw row
+            if (yr != xr) std::memmove(yr, xr, (size_t)V * sizeof(float));
+            continue;
+        }
+        float kth = lgr_neg_inf();
+        if (R.top_k > 0) {
+            sorted = y1;
+            std::sort(sorted.begin(), sorted.end(), [](float a, float b) { return a > b; });
+            kth = sorted[R.top_k - 1];
+        }
+        const float thr = lgr_threshold(kth, m, R.delta);
+        for (int v = 0; v < V; ++v) yr[v] = lgr_stage2(y1[v], thr);
+    }
     return 0;
 }
 

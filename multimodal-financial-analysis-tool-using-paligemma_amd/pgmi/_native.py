@@ -35,6 +35,13 @@ class PgmiConfig(ctypes.Structure):
     ]
 
 
+class PgmiLogitsParams(ctypes.Structure):  # pgmi_logits_params
+    _fields_ = [
+        ("rp", ctypes.c_float), ("pp", ctypes.c_float), ("fp", ctypes.c_float), ("top_k", ctypes.c_int),
+        ("min_p_delta", ctypes.c_float), ("suppress_id", ctypes.c_int), ("min_new_tokens", ctypes.c_int),
+    ]
+
+
 vp, i32, i64, f32, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
 
 # name -> (restype, argtypes); the exported surface of include/pgmi.h
@@ -113,6 +120,7 @@ SIGNATURES = {
     "pgmi_tune_gemm_shape": (i32, [i32, i32, i32, i32, i32, i32]),
     "pgmi_tune_attention": (i32, [i32]),
     "pgmi_sample_top_p": (i32, [vp, vp, i32, i32, f32, f32, vp, vp, vp, vp]),
+    "pgmi_logits_process_host": (i32, [vp, i32, i32, vp, vp, ctypes.POINTER(PgmiLogitsParams), vp, vp]),
     "pgmi_op_gemm": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "pgmi_op_gemm_strided": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "pgmi_op_rmsnorm": (i32, [vp, vp, vp, i32, i32, f32, vp, vp]),
