@@ -467,6 +467,33 @@ typedef struct pgmi_logits_params {
 int pgmi_logits_process_host(const float* x, int rows, int V, const uint32_t* history, const float* bias,
                              const pgmi_logits_params* params, const int32_t* emitted, float* y);
 
+/* ---- beam search: the rule, on the host only so far (csrc/beam_rule.h, DESIGN.md sec.1 (m): the device step and the
+ * KV gather are left out of the tree): transformers' _beam_search with do_sample=False, one stop
+ * token and early_stopping in {False, True}.  G groups (prompts) of K beams, G * K <= max_batch <= 16; C = 2K
+ * candidates per step; steps t = 0 .. n_tokens - 1, t = 0 picking from the prefill's logits (rows_in = 1, one row per
+ * group), every later one from the decode step's (rows_in = K).  A candidate of input row r scores
+ * s = fp32(fp32(x - lse_r) + run_r); the group keeps the first C by (s descending, row ascending, then x descending,
+ * token ascending within a row).  Candidates that are not eos carry on as the K running beams; eos candidates among
+ * the first K (on the last step: every one) contest the group's pool of K finished hypotheses with s / den[t + 1],
+ * den[n] = fp32(double(n) ** length_penalty) from the host.  A group is frozen (its pool final) once its best running
+ * score can no longer beat the pool's worst, or with early_stopping once the pool is full.
+ *
+ * The state is one caller-allocated blob of pgmi_beam_state_bytes() bytes, 16-byte aligned: a header, den, the running
+ * scores, flags, pool, the parent / token history of every step, and room for a device step's scratch.
+ * pgmi_beam_state_layout gives the offsets in 4-byte words: out[0..13] = den, run, heur, frozen, pool_score,
+ * pool_valid, pool_step, pool_parent, pool_token, hist_parent, hist_token, words of the state proper (what a final
+ * read copies), words in all, slices per row.  Sequences are rebuilt on the host: a pool slot (step, parent row,
+ * token) is walked back through hist_token[u][row], hist_parent[u][row], u = step - 1 .. 0.
+ * pgmi_beam_state_bytes is -1, and the others PGMI_E_ARG, unless 1 <= K <= 16, G * K <= 16, n_tokens >= 1 and
+ * 2K <= V <= 1.5M; eos is -1 (none) or in [0, V). */
+int64_t pgmi_beam_state_bytes(int G, int K, int n_tokens, int V);
+int pgmi_beam_state_layout(int G, int K, int n_tokens, int V, int64_t* out, int n);
+/* The rule on the host: no context, no GPU.  `state` is host memory of at least the state proper.  lse_in (fp32
+ * [G * rows_in]) may be NULL: the host then takes each row's log-sum-exp in fp64 itself; lse_out, n_open may be NULL.
+ * next_ids int64 [G * K], parent int32 [G * K] (batch rows g * K + beam; in range whatever the logits hold). */
+int pgmi_beam_reset_host(void* state, int G, int K, int n_tokens, int V, int eos, int early_stopping, const float* den);
+int pgmi_beam_step_host(void* state, const float* logits, int rows_in, int t, const float* lse_in, int64_t* next_ids,
+                        int32_t* parent, int32_t* n_open, float* lse_out);
 /* ---- single-op entry points (kernel-level parity tests) ---------------------------------- */
 /* out = epilogue(A[M,K] . W[N,K]^T): epi 0 store, 1 +bias, 2 +bias,gelu, 3 +bias,+res, 4 +res,
  * 6 fp32 out (out is float*), 7 GeGLU with up rows at W + N*K */

@@ -121,6 +121,10 @@ SIGNATURES = {
     "pgmi_tune_attention": (i32, [i32]),
     "pgmi_sample_top_p": (i32, [vp, vp, i32, i32, f32, f32, vp, vp, vp, vp]),
     "pgmi_logits_process_host": (i32, [vp, i32, i32, vp, vp, ctypes.POINTER(PgmiLogitsParams), vp, vp]),
+    "pgmi_beam_state_bytes": (i64, [i32, i32, i32, i32]),
+    "pgmi_beam_state_layout": (i32, [i32, i32, i32, i32, ctypes.POINTER(i64), i32]),
+    "pgmi_beam_reset_host": (i32, [vp, i32, i32, i32, i32, i32, i32, vp]),
+    "pgmi_beam_step_host": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "pgmi_op_gemm": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "pgmi_op_gemm_strided": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "pgmi_op_rmsnorm": (i32, [vp, vp, vp, i32, i32, f32, vp, vp]),
