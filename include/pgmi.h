@@ -372,6 +372,42 @@ int pgmi_debug_decode_buffer(pgmi_ctx* ctx, int which, void* buf, int64_t bytes,
 int pgmi_debug_decode_stage(pgmi_ctx* ctx, int stage, int layer, int B, const int64_t* ids, void* kv, int kv_batch,
                             int kv_max, const int32_t* kv_lens, const int32_t* positions, int ragged, const void* mask,
                             int mask_dtype, void* stream);
+/* Test hook: copy `bytes` bytes between a buffer of the language-model prefill's workspace and the caller's device
+ * memory `buf` (write != 0: buf -> workspace), row-major bf16: which 0 = Hs, the hidden state, and 1 = Tn, its norm
+ * ([max_batch * max_seq][hidden]: batch row b's slots at rows b * L ..); the scratch one row group (at most 8
+ * sequences) holds at a time, [min(max_batch, 8) * max_seq] rows of: 2 = QKV (unrotated q|k|v, written only where the
+ * plan has no RoPE epilogue), 3 = Qr (rotated q, heads * head_dim), 4 = AO (attention output, hidden), 5 = ACT
+ * (intermediate); 6 = lastrows ([max_batch][hidden], each sequence's last row), 7 = dAO ([max_batch][hidden], the
+ * last-row tail's combined attention output).  Stream-ordered.  PGMI_E_ARG: a byte count outside the buffer. */
+int pgmi_debug_prefill_buffer(pgmi_ctx* ctx, int which, void* buf, int64_t bytes, int write, void* stream);
+/* Test hook: run ONE stage of the language-model prefill for ONE row group (batch rows group * 8 ..) through the
+ * prefill's own launch code (the functions pgmi_lm_forward's body calls, with the same arguments), on the prefill
+ * workspace (pgmi_debug_prefill_buffer):
+ *   0  the entry, for the whole batch (group ignored): merge (ids, image_feats) or embeds x bf16(sqrt(hidden)),
+ *      then layer 0's input RMSNorm of every group                              ids / feats / embeds -> Hs, Tn
+ *   1  q|k|v with RoPE and the KV append: the fused epilogue, or the GEMM (partial slabs where the plan splits)
+ *      and the RoPE kernel, whichever the shape's plan gives                    Tn -> Qr, K/V rows
+ *   2  attention over cache rows [0, kv_start + L) (ragged: [0, kv_start + lens[b]))   Qr, K/V -> AO
+ *   3  o_proj partial slabs, their sum + residual, the post-attention norm      AO, Hs -> Hs, Tn
+ *   4  gate|up + GeGLU                                                          Tn -> ACT
+ *   5  down partial slabs, their sum + residual, the next layer's input norm (last layer: the final norm)
+ *                                                                               ACT, Hs -> Hs, Tn
+ *   6  the logits by logits_rows (layer ignored): 0 every row's (Tn -> logits); 1 each sequence's last row (ragged:
+ *      row lens[b] - 1) copied to lastrows, then final norm + lm_head; 2 final norm + lm_head of lastrows as
+ *      stage 7 left it                                                          Tn / Hs -> lastrows, logits
+ *   7  the last layer's last-row-only tail of logits_rows == 2 (after stage 1 of that layer): the last row's
+ *      attention (kv_start + L <= the config's max_kv: the decode step's flash-decoding; else the prefill kernel),
+ *      o_proj, MLP and residuals                                                Qr, K/V, Hs -> lastrows
+ * Every other argument is pgmi_lm_forward_ragged's, lens == NULL being the lock-step call (pgmi_lm_forward).  Every
+ * call copies the host positions to the device and sets the ragged rows' lengths, as those calls do before their
+ * launches.  Eager only: it never replays or captures a graph, and returns PGMI_E_STATE inside a stream capture.
+ * PGMI_E_ARG: an unknown stage, a layer (stages 1..5, 7) or group (stages 1..7) out of range, stage 7 outside the
+ * last layer of a lock-step logits_rows 2 call with L > 1, and everything pgmi_lm_forward(_ragged) refuses.  The
+ * final-hidden rows (pgmi_lm_final_hidden) are invalid afterwards. */
+int pgmi_debug_prefill_stage(pgmi_ctx* ctx, int stage, int layer, int group, const int64_t* ids,
+                             const void* image_feats, int n_img_rows, const void* embeds, int B, int L,
+                             const int64_t* positions, const int32_t* lens, void* kv, int kv_batch, int kv_max,
+                             int kv_start, float* logits, int logits_rows, void* stream);
 
 /* Image preprocessing on the GPU (processing_paligemma.py:13-49, process_images): PIL-exact
  * BICUBIC resize of one decoded RGB image (uint8 HWC, device memory, H x W) to out_h x out_w,

@@ -993,8 +993,20 @@ int pgmi_embed(pgmi_ctx* x, const int64_t* ids, int rows, void* out, void* strea
 static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
                    const void* embeds, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
                    int logits_rows, bool ragged);
-static int lm_rows(pgmi_ctx* x, hipStream_t s, int b0, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start,
-                   float* logits, int logits_rows, bool ragged);
+
+// One prefill row group's launches, shared by lm_rows and the stage hook (pgmi_debug_prefill_stage): what the
+// stages read besides the context.  A group's rows of Hs / Tn / lastrows, its positions, lengths, KV rows and
+// logits are its slice of the batch's (b0); QKV, Qr, AO, ACT and the split-K workspace are scratch the groups share.
+struct PrefillRun {
+    hipStream_t s;
+    int b0, B, L;            // the group's first batch row, its rows, the slots of a row
+    void* kv;
+    int kv_batch, kv_max, kv_start;
+    float* logits;           // the batch's logits (lm_logits takes the group's slice)
+    int logits_rows;
+    bool ragged;
+};
+static int lm_rows(pgmi_ctx* x, const PrefillRun& r);
 
 static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows, const void* embeds,
                       int B, int L, const int64_t* positions, const int32_t* lens, bool ragged, void* kv, int kv_batch,
@@ -1015,10 +1027,13 @@ int pgmi_lm_forward_ragged(pgmi_ctx* x, const int64_t* ids, const void* image_fe
                       kv_start, logits, logits_rows, stream);
 }
 
-static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows, const void* embeds,
-                      int B, int L, const int64_t* positions, const int32_t* lens, bool ragged, void* kv, int kv_batch,
-                      int kv_max, int kv_start, float* logits, int logits_rows, void* stream) {
+// What a language-model prefill does before its launches, shared by lm_forward and the stage hook
+// (pgmi_debug_prefill_stage): the argument checks, the ragged rows' lengths and the positions to the device.
+static int lm_begin(pgmi_ctx* x, const int64_t* ids, const void* embeds, int B, int L, const int64_t* positions,
+                    const int32_t* lens, bool ragged, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
+                    int* logits_rows_io, void* stream) {
     int rc;
+    int logits_rows = *logits_rows_io;
     if ((rc = ensure_prepared(x))) return rc;
     const pgmi_config& c = x->c;
     if (B < 1 || B > c.max_batch || B > kv_batch) return fail(PGMI_E_ARG, "batch exceeds capacity");
@@ -1044,6 +1059,17 @@ static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, 
                           (hipStream_t)stream));
     // Tn is overwritten from here on: no row of it is valid until this call has succeeded
     x->tn_rows = 0;
+    *logits_rows_io = logits_rows;
+    return 0;
+}
+
+static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows, const void* embeds,
+                      int B, int L, const int64_t* positions, const int32_t* lens, bool ragged, void* kv, int kv_batch,
+                      int kv_max, int kv_start, float* logits, int logits_rows, void* stream) {
+    int rc;
+    if ((rc = lm_begin(x, ids, embeds, B, L, positions, lens, ragged, kv, kv_batch, kv_max, kv_start, logits,
+                       &logits_rows, stream)))
+        return rc;
     const std::vector<intptr_t> key{2, (intptr_t)ids, (intptr_t)image_feats, n_img_rows, (intptr_t)embeds, B, L,
                                     (intptr_t)kv, kv_batch, kv_max, kv_start, (intptr_t)logits, logits_rows,
                                     (intptr_t)ragged};
@@ -1057,9 +1083,9 @@ static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, 
     return 0;
 }
 
-static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
-                   const void* embeds, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
-                   int logits_rows, bool ragged) {
+// the prefill's entry, for the whole batch: the merged (or given) embeddings x the normalizer -> Hs
+static void lm_entry(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
+                     const void* embeds, int B, int L, bool ragged) {
     const pgmi_config& c = x->c;
     // ragged: row b holds lens[b] tokens (d_rlens, set outside the graph), the rest of its L slots is padding
     const int* rlens = ragged ? x->d_rlens : nullptr;
@@ -1073,126 +1099,219 @@ static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* i
                     c.image_token_index, c.pad_token_id, (float)std::sqrt((double)H), normalizer, nullptr,
                     reinterpret_cast<int*>(x->dids_tmp), x->Hs, rlens);
     }
+}
+
+static int lm_body(pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
+                   const void* embeds, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
+                   int logits_rows, bool ragged) {
+    lm_entry(x, s, ids, image_feats, n_img_rows, embeds, B, L, ragged);
     // the layers: row groups of at most kPrefillGroup sequences, one after the other (the merge above ran for the
     // whole batch: the k-th <image> token of the batch takes image row k); a group's rows of Hs / Tn, its positions,
     // lengths, KV rows and logits are its slice of the batch's, everything else is scratch that the groups share
     for (int b0 = 0; b0 < B; b0 += kPrefillGroup) {
-        const int r = lm_rows(x, s, b0, std::min(kPrefillGroup, B - b0), L, kv, kv_batch, kv_max, kv_start, logits,
-                              logits_rows, ragged);
-        if (r) return r;
+        const PrefillRun r{s, b0, std::min(kPrefillGroup, B - b0), L, kv, kv_batch, kv_max, kv_start, logits,
+                           logits_rows, ragged};
+        if (int rc = lm_rows(x, r)) return rc;
     }
     return 0;
 }
 
-static int lm_rows(pgmi_ctx* x, hipStream_t s, int b0, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start,
-                   float* logits, int logits_rows, bool ragged) {
+// the group's slices and the per-layer cache rows
+static uint16_t* run_hs(const pgmi_ctx* x, const PrefillRun& r) { return x->Hs + (size_t)r.b0 * r.L * x->c.t_hidden; }
+static uint16_t* run_tn(const pgmi_ctx* x, const PrefillRun& r) { return x->Tn + (size_t)r.b0 * r.L * x->c.t_hidden; }
+static uint16_t* run_lastrows(const pgmi_ctx* x, const PrefillRun& r) {
+    return x->lastrows + (size_t)r.b0 * x->c.t_hidden;
+}
+static long run_kvb(const pgmi_ctx* x, const PrefillRun& r) {
+    return (long)r.kv_max * x->c.t_kv_heads * x->c.t_head_dim;
+}
+// layer i's K (v = 0) or V (v = 1) rows of the group
+static uint16_t* run_cache(const pgmi_ctx* x, const PrefillRun& r, int i, int v) {
+    const long kvb = run_kvb(x, r);
+    return reinterpret_cast<uint16_t*>(r.kv) + (long)r.b0 * kvb + ((long)(i * 2 + v) * r.kv_batch) * kvb;
+}
+// logits_rows == 2: the last layer's post-projection work runs for the last row of each sequence alone
+static bool run_last_only(const pgmi_ctx* x, const PrefillRun& r) {
+    return r.logits_rows == 2 && r.L > 1 && x->c.t_layers > 0;
+}
+
+// input RMSNorm of layer 0; every later RMSNorm (and the final norm) is fused with the
+// preceding projection's split-K reduction + residual (splitk_res_norm)
+static void lm_in_norm(pgmi_ctx* x, const PrefillRun& r) {
     const pgmi_config& c = x->c;
-    const int* rlens = ragged ? x->d_rlens + b0 : nullptr;
-    const int* rkeys = ragged ? x->d_rlens + kMaxRows + b0 : nullptr;
-    const int H = c.t_hidden, R = B * L, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
+    rmsnorm(r.s, run_hs(x, r), c.t_layers ? x->w.t[0].in_norm : x->w.final_norm, c.t_rms_eps, run_tn(x, r), r.B * r.L,
+            c.t_hidden);
+}
+
+// layer i's q|k|v with RoPE and the KV append: Tn -> Qr, the cache rows
+static void lm_qkv(pgmi_ctx* x, const PrefillRun& r, int i) {
+    const pgmi_config& c = x->c;
+    hipStream_t s = r.s;
+    const int H = c.t_hidden, R = r.B * r.L, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
     const int QKVN = (NH + 2 * NKV) * HD;
-    const float eps = c.t_rms_eps;
-    const uint16_t* E = x->w.embed;
-    uint16_t* const Hs = x->Hs + (size_t)b0 * L * H;
-    uint16_t* const Tn = x->Tn + (size_t)b0 * L * H;
-    uint16_t* const lastrows = x->lastrows + (size_t)b0 * H;
-    const int64_t* const dpos = x->dpos + (size_t)b0 * L;
-    logits += (size_t)b0 * (logits_rows == 0 ? L : 1) * c.t_vocab;
-    const long kvd = (long)NKV * HD, kvb = (long)kv_max * kvd;
-    uint16_t* kvp = reinterpret_cast<uint16_t*>(kv) + (long)b0 * kvb;  // the group's rows of every layer's K and V
-    const uint16_t* fnorm = x->w.final_norm;
-    const bool last_only = logits_rows == 2 && L > 1 && c.t_layers > 0;
-    // input RMSNorm of layer 0; every later RMSNorm (and the final norm) is fused with the
-    // preceding projection's split-K reduction + residual (splitk_res_norm)
-    rmsnorm(s, Hs, c.t_layers ? x->w.t[0].in_norm : fnorm, eps, Tn, R, H);
-    for (int i = 0; i < c.t_layers; ++i) {
-        const TextLayerW& w = x->w.t[i];
-        uint16_t* Kc = kvp + ((long)(i * 2 + 0) * kv_batch) * kvb;
-        uint16_t* Vc = kvp + ((long)(i * 2 + 1) * kv_batch) * kvb;
-        EpiArgs q{};
-        q.out = x->QKV; q.ldo = QKVN;
-        // RoPE + KV append in the projection's epilogue where the shape's plan allows it
-        q.rpos = dpos; q.cosT = x->cosT; q.sinT = x->sinT; q.max_pos = c.t_max_pos;
-        q.q_out = x->Qr; q.kc = Kc; q.vc = Vc; q.kv_b_stride = kvb; q.kv_start = kv_start;
-        q.L = L; q.nh = NH; q.nkv = NKV;
-        if (HD != 256 || !gemm_qkv_rope(s, Tn, H, w.qkv, H, R, QKVN, H, q)) {
-            int sp = gemm(s, Tn, H, w.qkv, H, R, QKVN, H, EPI_STORE, q, x->ws, x->ws_bytes, 0, true);
-            rope_kv_append(s, x->QKV, x->ws, sp, B, L, NH, NKV, dpos, x->cosT, x->sinT, c.t_max_pos, x->Qr, Kc, Vc,
-                           kvb, kv_start);
-        }
-        AttnArgs a{};
-        a.q = x->Qr; a.q_b_stride = (long)L * NH * HD; a.q_row_stride = NH * HD; a.q_head_stride = HD;
-        a.k = Kc; a.k_b_stride = kvb; a.k_row_stride = (int)kvd; a.k_head_stride = HD;
-        a.v = Vc; a.v_b_stride = kvb; a.v_row_stride = (int)kvd; a.v_head_stride = HD;
-        a.o = x->AO; a.o_b_stride = (long)L * H; a.o_row_stride = H; a.o_head_stride = HD;
-        a.Lq = L; a.Lk = kv_start + L; a.G = NH / NKV; a.n_kv = NKV; a.B = B;
-        a.scale = 1.0f / std::sqrt((float)HD);  // / math.sqrt(head_dim) (:266): exact power of two
-        a.ws = x->ws; a.ws_floats = (long)(x->ws_bytes / sizeof(float));
-        a.klen = rkeys;  // ragged: row b's real tokens attend its own real keys only
-        if (last_only && i + 1 == c.t_layers) {
-            // logits_rows == 2, last layer: the K/V rows of every token are written above (the cache
-            // the decode loop reads); the rest of the layer feeds only the final hidden state, and the
-            // caller reads that for the last row alone, so attention, o_proj, the MLP and the final
-            // norm run for the last row of each sequence (row-wise ops: the same values as the
-            // all-row pass up to GEMV-vs-GEMM accumulation order), on the decode GEMVs
-            a.q = x->Qr + (size_t)(L - 1) * NH * HD;
-            a.o = x->dAO; a.o_b_stride = (long)H;
-            a.Lq = 1;
-            HIPCHK(hipMemcpy2DAsync(lastrows, (size_t)H * 2, Hs + (size_t)(L - 1) * H, (size_t)L * H * 2,
-                                    (size_t)H * 2, B, hipMemcpyDeviceToDevice, s));
-            if (kv_start + L <= c.max_kv) {
-                // one query row over the prompt's keys: the decode step's flash-decoding (64-key chunks
-                // in parallel, kv_len from a device step record set by a memset node) and its o_proj
-                // GEMV with the chunk combine in the prologue; a single 16-row prefill workgroup
-                // would walk every key alone
-                a.Lk = 0;
-                HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&x->pstep->kv_len), kv_start + L - 1, 1, s));
-                a.mask = x->d_zero; a.mask_b_stride = 0; a.mask_k_stride = 0; a.mask_round = 1;
-                attention_decode(s, a, x->pstep, kv_start + L, x->opart, x->max_chunks);
-                gemv_o_attn(s, B, NH, x->opart, x->max_chunks, x->pstep, w.o, H, lastrows,
-                            B >= gemv_mf_min_batch() ? x->dAO : nullptr);
-            } else {
-                attention_prefill(s, 256, a);
-                gemv_res(s, B, NH * HD, x->dAO, w.o, H, lastrows, x->ws);
-            }
-            gemv_geglu(s, B, lastrows, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
-                       pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
-            gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, lastrows, x->ws, pk_use(x, B, PK_DOWN, w.pk_down));
-            break;
-        }
-        attention_prefill(s, 256, a);
-        EpiArgs o{};
-        o.res = Hs; o.ldr = H; o.out = Hs; o.ldo = H;
-        int sp = gemm(s, x->AO, H, w.o, H, R, H, NH * HD, EPI_RES, o, x->ws, x->ws_bytes, 0, true);
-        splitk_res_norm(s, x->ws, sp, nullptr, Hs, w.post_norm, nullptr, eps, Tn, R, H);
-        EpiArgs g{};
-        g.out = x->ACT; g.ldo = c.t_intermediate;
-        const bool probe = x->probe_on && (size_t)(4 * i + 3) < x->probe_ev.size();
-        // probe: the GEMM kernel itself carries the events (its own start / end, gemm_probe_events)
-        if (probe) gemm_probe_events(x->probe_ev[4 * i], x->probe_ev[4 * i + 1]);
-        gemm(s, Tn, H, w.gate_up, H, R, c.t_intermediate, H, EPI_GEGLU, g, x->ws, x->ws_bytes, c.t_intermediate);
-        EpiArgs d{};
-        d.res = Hs; d.ldr = H; d.out = Hs; d.ldo = H;
-        if (probe) gemm_probe_events(x->probe_ev[4 * i + 2], x->probe_ev[4 * i + 3]);
-        sp = gemm(s, x->ACT, c.t_intermediate, w.down, c.t_intermediate, R, H, c.t_intermediate, EPI_RES, d, x->ws,
-                  x->ws_bytes, 0, true);
-        const bool last = i + 1 == c.t_layers;
-        splitk_res_norm(s, x->ws, sp, nullptr, Hs, last ? fnorm : x->w.t[i + 1].in_norm, nullptr, eps, Tn, R, H);
+    const long kvb = run_kvb(x, r);
+    const TextLayerW& w = x->w.t[i];
+    uint16_t* const Tn = run_tn(x, r);
+    const int64_t* const dpos = x->dpos + (size_t)r.b0 * r.L;
+    uint16_t* Kc = run_cache(x, r, i, 0);
+    uint16_t* Vc = run_cache(x, r, i, 1);
+    EpiArgs q{};
+    q.out = x->QKV; q.ldo = QKVN;
+    // RoPE + KV append in the projection's epilogue where the shape's plan allows it
+    q.rpos = dpos; q.cosT = x->cosT; q.sinT = x->sinT; q.max_pos = c.t_max_pos;
+    q.q_out = x->Qr; q.kc = Kc; q.vc = Vc; q.kv_b_stride = kvb; q.kv_start = r.kv_start;
+    q.L = r.L; q.nh = NH; q.nkv = NKV;
+    if (HD != 256 || !gemm_qkv_rope(s, Tn, H, w.qkv, H, R, QKVN, H, q)) {
+        int sp = gemm(s, Tn, H, w.qkv, H, R, QKVN, H, EPI_STORE, q, x->ws, x->ws_bytes, 0, true);
+        rope_kv_append(s, x->QKV, x->ws, sp, r.B, r.L, NH, NKV, dpos, x->cosT, x->sinT, c.t_max_pos, x->Qr, Kc, Vc,
+                       kvb, r.kv_start);
     }
-    if (logits_rows == 0) {
-        EpiArgs l{};  // Tn holds the final RMSNorm (modeling_gemma.py:379)
-        l.out_f32 = logits; l.ldo = c.t_vocab;
-        gemm(s, Tn, H, E, H, R, c.t_vocab, H, EPI_F32, l, x->ws, x->ws_bytes);
+}
+
+// layer i's attention arguments: every query row of the group over the cache rows [0, kv_start + L)
+static AttnArgs lm_attn_args(const pgmi_ctx* x, const PrefillRun& r, int i) {
+    const pgmi_config& c = x->c;
+    const int H = c.t_hidden, NH = c.t_heads, NKV = c.t_kv_heads, HD = c.t_head_dim;
+    const long kvd = (long)NKV * HD, kvb = run_kvb(x, r);
+    AttnArgs a{};
+    a.q = x->Qr; a.q_b_stride = (long)r.L * NH * HD; a.q_row_stride = NH * HD; a.q_head_stride = HD;
+    a.k = run_cache(x, r, i, 0); a.k_b_stride = kvb; a.k_row_stride = (int)kvd; a.k_head_stride = HD;
+    a.v = run_cache(x, r, i, 1); a.v_b_stride = kvb; a.v_row_stride = (int)kvd; a.v_head_stride = HD;
+    a.o = x->AO; a.o_b_stride = (long)r.L * H; a.o_row_stride = H; a.o_head_stride = HD;
+    a.Lq = r.L; a.Lk = r.kv_start + r.L; a.G = NH / NKV; a.n_kv = NKV; a.B = r.B;
+    a.scale = 1.0f / std::sqrt((float)HD);  // / math.sqrt(head_dim) (:266): exact power of two
+    a.ws = x->ws; a.ws_floats = (long)(x->ws_bytes / sizeof(float));
+    // ragged: row b's real tokens attend its own real keys only
+    a.klen = r.ragged ? x->d_rlens + kMaxRows + r.b0 : nullptr;
+    return a;
+}
+
+// layer i's attention: Qr, the cache rows -> AO
+static void lm_attn(pgmi_ctx* x, const PrefillRun& r, int i) { attention_prefill(r.s, 256, lm_attn_args(x, r, i)); }
+
+// layer i's o_proj partial slabs, then their sum + residual and the post-attention norm: AO, Hs -> Hs, Tn
+static void lm_o_proj(pgmi_ctx* x, const PrefillRun& r, int i) {
+    const pgmi_config& c = x->c;
+    const int H = c.t_hidden, R = r.B * r.L;
+    const TextLayerW& w = x->w.t[i];
+    uint16_t* const Hs = run_hs(x, r);
+    EpiArgs o{};
+    o.res = Hs; o.ldr = H; o.out = Hs; o.ldo = H;
+    int sp = gemm(r.s, x->AO, H, w.o, H, R, H, c.t_heads * c.t_head_dim, EPI_RES, o, x->ws, x->ws_bytes, 0, true);
+    splitk_res_norm(r.s, x->ws, sp, nullptr, Hs, w.post_norm, nullptr, c.t_rms_eps, run_tn(x, r), R, H);
+}
+
+// layer i's gate|up + GeGLU: Tn -> ACT
+static void lm_gate_up(pgmi_ctx* x, const PrefillRun& r, int i) {
+    const pgmi_config& c = x->c;
+    const int H = c.t_hidden;
+    EpiArgs g{};
+    g.out = x->ACT; g.ldo = c.t_intermediate;
+    // probe: the GEMM kernel itself carries the events (its own start / end, gemm_probe_events)
+    const bool probe = x->probe_on && (size_t)(4 * i + 3) < x->probe_ev.size();
+    if (probe) gemm_probe_events(x->probe_ev[4 * i], x->probe_ev[4 * i + 1]);
+    gemm(r.s, run_tn(x, r), H, x->w.t[i].gate_up, H, r.B * r.L, c.t_intermediate, H, EPI_GEGLU, g, x->ws, x->ws_bytes,
+         c.t_intermediate);
+}
+
+// layer i's down partial slabs, then their sum + residual and the next input norm (the final norm after the last
+// layer): ACT, Hs -> Hs, Tn
+static void lm_down(pgmi_ctx* x, const PrefillRun& r, int i) {
+    const pgmi_config& c = x->c;
+    const int H = c.t_hidden, R = r.B * r.L;
+    uint16_t* const Hs = run_hs(x, r);
+    EpiArgs d{};
+    d.res = Hs; d.ldr = H; d.out = Hs; d.ldo = H;
+    const bool probe = x->probe_on && (size_t)(4 * i + 3) < x->probe_ev.size();
+    if (probe) gemm_probe_events(x->probe_ev[4 * i + 2], x->probe_ev[4 * i + 3]);
+    const int sp = gemm(r.s, x->ACT, c.t_intermediate, x->w.t[i].down, c.t_intermediate, R, H, c.t_intermediate,
+                        EPI_RES, d, x->ws, x->ws_bytes, 0, true);
+    const bool last = i + 1 == c.t_layers;
+    splitk_res_norm(r.s, x->ws, sp, nullptr, Hs, last ? x->w.final_norm : x->w.t[i + 1].in_norm, nullptr, c.t_rms_eps,
+                    run_tn(x, r), R, H);
+}
+
+// logits_rows == 2, last layer: the K/V rows of every token are written by lm_qkv (the cache
+// the decode loop reads); the rest of the layer feeds only the final hidden state, and the
+// caller reads that for the last row alone, so attention, o_proj, the MLP and the final
+// norm run for the last row of each sequence (row-wise ops: the same values as the
+// all-row pass up to GEMV-vs-GEMM accumulation order), on the decode GEMVs: Qr, the cache rows, Hs -> lastrows
+static int lm_last_row_tail(pgmi_ctx* x, const PrefillRun& r, int i) {
+    const pgmi_config& c = x->c;
+    hipStream_t s = r.s;
+    const int B = r.B, L = r.L, H = c.t_hidden, NH = c.t_heads, HD = c.t_head_dim;
+    const float eps = c.t_rms_eps;
+    const TextLayerW& w = x->w.t[i];
+    uint16_t* const lastrows = run_lastrows(x, r);
+    AttnArgs a = lm_attn_args(x, r, i);
+    a.q = x->Qr + (size_t)(L - 1) * NH * HD;
+    a.o = x->dAO; a.o_b_stride = (long)H;
+    a.Lq = 1;
+    HIPCHK(hipMemcpy2DAsync(lastrows, (size_t)H * 2, run_hs(x, r) + (size_t)(L - 1) * H, (size_t)L * H * 2,
+                            (size_t)H * 2, B, hipMemcpyDeviceToDevice, s));
+    if (r.kv_start + L <= c.max_kv) {
+        // one query row over the prompt's keys: the decode step's flash-decoding (64-key chunks
+        // in parallel, kv_len from a device step record set by a memset node) and its o_proj
+        // GEMV with the chunk combine in the prologue; a single 16-row prefill workgroup
+        // would walk every key alone
+        a.Lk = 0;
+        HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&x->pstep->kv_len), r.kv_start + L - 1, 1, s));
+        a.mask = x->d_zero; a.mask_b_stride = 0; a.mask_k_stride = 0; a.mask_round = 1;
+        attention_decode(s, a, x->pstep, r.kv_start + L, x->opart, x->max_chunks);
+        gemv_o_attn(s, B, NH, x->opart, x->max_chunks, x->pstep, w.o, H, lastrows,
+                    B >= gemv_mf_min_batch() ? x->dAO : nullptr);
     } else {
-        if (ragged)  // each row's last real token, lens[b] - 1
-            gather_last_rows(s, Hs, B, L, H, rlens, lastrows);
-        else if (!last_only)
-            HIPCHK(hipMemcpy2DAsync(lastrows, (size_t)H * 2, Hs + (size_t)(L - 1) * H, (size_t)L * H * 2,
+        attention_prefill(s, 256, a);
+        gemv_res(s, B, NH * HD, x->dAO, w.o, H, lastrows, x->ws);
+    }
+    gemv_geglu(s, B, lastrows, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
+               pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
+    gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, lastrows, x->ws, pk_use(x, B, PK_DOWN, w.pk_down));
+    return 0;
+}
+
+// the group's logits: every row's (logits_rows 0, Tn holds the final RMSNorm, modeling_gemma.py:379) or each
+// sequence's last row's (lastrows: copied or gathered here, or lm_last_row_tail's)
+static int lm_logits(pgmi_ctx* x, const PrefillRun& r) {
+    const pgmi_config& c = x->c;
+    hipStream_t s = r.s;
+    const int B = r.B, L = r.L, H = c.t_hidden;
+    const uint16_t* E = x->w.embed;
+    uint16_t* const lastrows = run_lastrows(x, r);
+    float* const logits = r.logits + (size_t)r.b0 * (r.logits_rows == 0 ? L : 1) * c.t_vocab;
+    if (r.logits_rows == 0) {
+        EpiArgs l{};
+        l.out_f32 = logits; l.ldo = c.t_vocab;
+        gemm(s, run_tn(x, r), H, E, H, B * L, c.t_vocab, H, EPI_F32, l, x->ws, x->ws_bytes);
+    } else {
+        if (r.ragged)  // each row's last real token, lens[b] - 1
+            gather_last_rows(s, run_hs(x, r), B, L, H, x->d_rlens + r.b0, lastrows);
+        else if (!run_last_only(x, r))
+            HIPCHK(hipMemcpy2DAsync(lastrows, (size_t)H * 2, run_hs(x, r) + (size_t)(L - 1) * H, (size_t)L * H * 2,
                                     (size_t)H * 2, B, hipMemcpyDeviceToDevice, s));
         int nparts = 0;
-        gemv_logits(s, B, lastrows, fnorm, eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts, nullptr, nullptr,
-                    nullptr, nullptr, 1, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed));
+        gemv_logits(s, B, lastrows, x->w.final_norm, c.t_rms_eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts,
+                    nullptr, nullptr, nullptr, nullptr, 1, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed));
     }
+    return 0;
+}
+
+static int lm_rows(pgmi_ctx* x, const PrefillRun& r) {
+    const int layers = x->c.t_layers;
+    int rc;
+    lm_in_norm(x, r);
+    for (int i = 0; i < layers; ++i) {
+        lm_qkv(x, r, i);
+        if (run_last_only(x, r) && i + 1 == layers) {
+            if ((rc = lm_last_row_tail(x, r, i))) return rc;
+            break;
+        }
+        lm_attn(x, r, i);
+        lm_o_proj(x, r, i);
+        lm_gate_up(x, r, i);
+        lm_down(x, r, i);
+    }
+    if ((rc = lm_logits(x, r))) return rc;
     LAUNCHCHK();
     return 0;
 }
@@ -2270,6 +2389,83 @@ int pgmi_debug_decode_buffer(pgmi_ctx* x, int which, void* buf, int64_t bytes, i
         default: return fail(PGMI_E_ARG, "decode buffer: 0 h, 1 act, 2 logits, 3 q, 4 ao, 5 hn, 6 ssq, 7 next ids");
     }
     if (bytes < 1 || bytes > cap) return fail(PGMI_E_ARG, "decode buffer: byte count outside the buffer");
+    HIPCHK(hipMemcpyAsync(write ? p : buf, write ? buf : p, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+int pgmi_debug_prefill_stage(pgmi_ctx* x, int stage, int layer, int group, const int64_t* ids, const void* image_feats,
+                             int n_img_rows, const void* embeds, int B, int L, const int64_t* positions,
+                             const int32_t* lens, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
+                             int logits_rows, void* stream) {
+    if (!x) return fail(PGMI_E_ARG, "null argument");
+    if (stage < 0 || stage > 7)
+        return fail(PGMI_E_ARG, "prefill stage: 0 entry, 1 q|k|v, 2 attention, 3 o_proj, 4 gate|up, 5 down, 6 logits, "
+                                "7 last-row tail");
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIPCHK(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(PGMI_E_STATE, "pgmi_debug_prefill_stage inside a stream capture");
+    const bool ragged = lens != nullptr;
+    int rc;
+    // everything lm_forward refuses, then the row lengths and the positions to the device, as it does
+    if ((rc = lm_begin(x, ids, embeds, B, L, positions, lens, ragged, kv, kv_batch, kv_max, kv_start, logits,
+                       &logits_rows, stream)))
+        return rc;
+    const pgmi_config& c = x->c;
+    const int groups = (B + kPrefillGroup - 1) / kPrefillGroup;
+    if (stage != 0 && (group < 0 || group >= groups)) return fail(PGMI_E_ARG, "group out of range");
+    if (stage != 0 && stage != 6 && (layer < 0 || layer >= c.t_layers)) return fail(PGMI_E_ARG, "layer out of range");
+    const auto run = [&](int g) {
+        const int b0 = g * kPrefillGroup;
+        return PrefillRun{s, b0, std::min(kPrefillGroup, B - b0), L, kv, kv_batch, kv_max, kv_start, logits, logits_rows,
+                          ragged};
+    };
+    if (stage == 0) {
+        lm_entry(x, s, ids, image_feats, n_img_rows, embeds, B, L, ragged);
+        for (int g = 0; g < groups; ++g) lm_in_norm(x, run(g));
+        LAUNCHCHK();
+        return 0;
+    }
+    const PrefillRun r = run(group);
+    switch (stage) {
+        case 1: lm_qkv(x, r, layer); break;
+        case 2: lm_attn(x, r, layer); break;
+        case 3: lm_o_proj(x, r, layer); break;
+        case 4: lm_gate_up(x, r, layer); break;
+        case 5: lm_down(x, r, layer); break;
+        case 6:
+            if ((rc = lm_logits(x, r))) return rc;
+            break;
+        default:
+            if (!run_last_only(x, r) || layer + 1 != c.t_layers)
+                return fail(PGMI_E_ARG, "prefill stage 7: the last layer of a lock-step logits_rows 2 call with L > 1");
+            if ((rc = lm_last_row_tail(x, r, layer))) return rc;
+    }
+    LAUNCHCHK();
+    return 0;
+}
+
+int pgmi_debug_prefill_buffer(pgmi_ctx* x, int which, void* buf, int64_t bytes, int write, void* stream) {
+    int rc;
+    if (!x || !buf) return fail(PGMI_E_ARG, "null argument");
+    if ((rc = ensure_prepared(x))) return rc;
+    const pgmi_config& c = x->c;
+    const int64_t R = (int64_t)c.max_batch * c.max_seq, RG = (int64_t)std::min(c.max_batch, kPrefillGroup) * c.max_seq;
+    void* p;
+    int64_t cap;
+    switch (which) {
+        case 0: p = x->Hs; cap = R * c.t_hidden * 2; break;
+        case 1: p = x->Tn; cap = R * c.t_hidden * 2; break;
+        case 2: p = x->QKV; cap = RG * (c.t_heads + 2 * c.t_kv_heads) * c.t_head_dim * 2; break;
+        case 3: p = x->Qr; cap = RG * c.t_heads * c.t_head_dim * 2; break;
+        case 4: p = x->AO; cap = RG * c.t_hidden * 2; break;
+        case 5: p = x->ACT; cap = RG * c.t_intermediate * 2; break;
+        case 6: p = x->lastrows; cap = (int64_t)c.max_batch * c.t_hidden * 2; break;
+        case 7: p = x->dAO; cap = (int64_t)c.max_batch * c.t_hidden * 2; break;
+        default:
+            return fail(PGMI_E_ARG, "prefill buffer: 0 Hs, 1 Tn, 2 QKV, 3 Qr, 4 AO, 5 ACT, 6 lastrows, 7 dAO");
+    }
+    if (bytes < 1 || bytes > cap) return fail(PGMI_E_ARG, "prefill buffer: byte count outside the buffer");
     HIPCHK(hipMemcpyAsync(write ? p : buf, write ? buf : p, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }

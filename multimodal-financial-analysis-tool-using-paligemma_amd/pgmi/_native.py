@@ -116,6 +116,9 @@ SIGNATURES = {
     "pgmi_decode_kernel": (i32, [vp, i32, i32, i32, vp]),
     "pgmi_debug_decode_buffer": (i32, [vp, i32, vp, i64, i32, vp]),
     "pgmi_debug_decode_stage": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp]),
+    "pgmi_debug_prefill_buffer": (i32, [vp, i32, vp, i64, i32, vp]),
+    "pgmi_debug_prefill_stage": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32,
+                                       vp]),
     "pgmi_tune_gemm": (i32, [i32, i32]),
     "pgmi_tune_gemm_shape": (i32, [i32, i32, i32, i32, i32, i32]),
     "pgmi_tune_attention": (i32, [i32]),

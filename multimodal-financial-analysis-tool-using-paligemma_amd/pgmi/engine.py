@@ -671,6 +671,54 @@ class Engine:
                                                   int(bool(write)), self._s()), "pgmi_debug_decode_buffer")
         return t
 
+    def prefill_stage(self, stage: int, layer: int, group: int, kv: torch.Tensor, kv_start: int, positions,
+                      logits: torch.Tensor, ids: torch.Tensor = None, image_feats: torch.Tensor = None,
+                      embeds: torch.Tensor = None, B: int = None, L: int = None, logits_rows: int = 0,
+                      lens=None) -> None:
+        """One stage of the language-model prefill for one row group (batch rows 8 * group ..) through the prefill's
+        own launch code (pgmi_debug_prefill_stage: a test hook): 0 entry (whole batch), 1 q|k|v + RoPE + KV append,
+        2 attention, 3 o_proj + residual + norm, 4 gate|up, 5 down + residual + norm, 6 logits, 7 the last-row tail
+        of logits_rows 2, on the workspace prefill_buffer reads and writes.  The arguments are lm_forward's: ids
+        (B, L) int64 or embeds (B, L, hidden) bf16 on the device (else B and L), host positions, lens for a ragged
+        batch, and the caller's fp32 logits tensor."""
+        self._ready()
+        for t in (ids, image_feats, embeds, logits):
+            if t is not None and (t.device != self.device or not t.is_contiguous()):
+                raise ValueError("prefill_stage: contiguous tensors on the engine's device")
+        if ids is not None:
+            B, L = ids.shape
+        elif embeds is not None:
+            B, L = embeds.shape[0], embeds.shape[1]
+        if B is None or L is None:
+            raise ValueError("prefill_stage: ids, embeds or B and L")
+        nimg = 0 if image_feats is None else image_feats.numel() // image_feats.shape[-1]
+        pos = torch.as_tensor(positions, dtype=torch.int64).cpu()
+        pos = torch.broadcast_to(pos.reshape(pos.shape[0] if pos.dim() > 1 else 1, -1), (B, L)).contiguous()
+        ln = None
+        if lens is not None:
+            ln = torch.as_tensor(lens).detach().to("cpu", torch.int32).reshape(-1).contiguous()
+            if ln.numel() != B:
+                raise ValueError(f"lens has {ln.numel()} entries for a batch of {B}")
+        rows = B * (L if logits_rows == 0 else 1)
+        if logits.dtype is not torch.float32 or logits.numel() < rows * self.cfgd["t_vocab"]:
+            raise ValueError("prefill_stage: logits must be fp32 with room for the call's rows")
+        N.check(self.lib.pgmi_debug_prefill_stage(self.ctx, int(stage), int(layer), int(group), N.ptr(ids),
+                                                  N.ptr(image_feats), nimg, N.ptr(embeds), int(B), int(L),
+                                                  pos.data_ptr(), N.ptr(ln), kv.data_ptr(), kv.shape[2], kv.shape[3],
+                                                  int(kv_start), logits.data_ptr(), int(logits_rows), self._s()),
+                "pgmi_debug_prefill_stage")
+
+    def prefill_buffer(self, which: int, t: torch.Tensor, write: bool = False) -> torch.Tensor:
+        """Copy the first rows of the prefill workspace's Hs (0) / Tn (1) / QKV (2) / Qr (3) / AO (4) / ACT (5) /
+        lastrows (6) / dAO (7) into the contiguous device tensor t, or (write) t into the workspace
+        (pgmi_debug_prefill_buffer: a test hook)."""
+        self._ready()
+        if t.device != self.device or not t.is_contiguous():
+            raise ValueError("prefill_buffer: a contiguous tensor on the engine's device")
+        N.check(self.lib.pgmi_debug_prefill_buffer(self.ctx, int(which), t.data_ptr(), t.numel() * t.element_size(),
+                                                   int(bool(write)), self._s()), "pgmi_debug_prefill_buffer")
+        return t
+
     def argmax(self, logits: torch.Tensor) -> torch.Tensor:
         l2 = logits.reshape(-1, logits.shape[-1]).contiguous()
         out = torch.empty(l2.shape[0], dtype=torch.int64, device=self.device)
