@@ -18,6 +18,7 @@
 #include "common.h"
 #include "launch.h"
 
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 
@@ -1179,6 +1180,11 @@ static void launch_fa(hipStream_t s, const AttnArgs& a) {
 static int g_attn_force = -1;
 
 void attention_force_variant(int v) { g_attn_force = v; }
+
+long tune_epoch(int bump) {
+    static std::atomic<long> n{0};
+    return n += bump;
+}
 
 template <int HD>
 static void launch_fa_variant(hipStream_t s, const AttnArgs& a, int rk) {

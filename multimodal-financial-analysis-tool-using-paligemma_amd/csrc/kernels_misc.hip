@@ -10,10 +10,28 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "../../include/pgmi.h"
 #include "common.h"
 #include "launch.h"
 
+namespace {
+
+using namespace pgmi;
+
+__global__ void k_convert(const void* src, int dtype, long n, uint16_t* dst) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        if (dtype == PGMI_DTYPE_F32) dst[i] = f2bf(reinterpret_cast<const float*>(src)[i]);
+        else dst[i] = f2bf((float)reinterpret_cast<const _Float16*>(src)[i]);
+    }
+}
+
+}  // namespace
+
 namespace pgmi {
+
+void convert_to_bf16(hipStream_t s, const void* src, int dtype, long n, uint16_t* dst) {
+    hipLaunchKernelGGL(k_convert, dim3(1024), dim3(256), 0, s, src, dtype, n, dst);
+}
 
 // ---------------------------------------------------------------- block reductions
 template <int NT>

@@ -214,6 +214,9 @@ constexpr int kAttnPartStride = 16 * 256 + 32;  // floats per (b, kv head, chunk
 size_t attention_decode_part_floats(int B, int n_kv, int max_chunks);
 int attention_prefill_max_keys(int head_dim);
 void attention_force_variant(int v);  // tuning hook (kernels_attn.hip); -1 = measured choice
+// the process-wide count of tuning calls (pgmi_tune_gemm, pgmi_tune_gemm_shape, pgmi_tune_attention), an element
+// of every prefill graph key (engine_graph.h): bump = 1 counts one more call; returns the count
+__attribute__((visibility("hidden"))) long tune_epoch(int bump = 0);
 
 // ---------------------------------------------------------------- per-module entry points (kernels_modules.hip)
 // reference-order attention with the probability matrix and an additive mask (module forwards)
@@ -275,6 +278,9 @@ void rope_kv_append(hipStream_t s, const uint16_t* qkv, const float* ws, int spl
 void patchify(hipStream_t s, const void* px, int px_is_f32, int B, int C, int H, int W, int P, int Kpad,
               uint16_t* out);
 void fill_synthetic(hipStream_t s, uint16_t* dst, long n, uint64_t key, float scale, float offset);
+// dst[i] = bf16(src[i]), src fp32 or fp16 (PGMI_DTYPE_F32 / PGMI_DTYPE_F16), round to nearest even
+__attribute__((visibility("hidden"))) void convert_to_bf16(hipStream_t s, const void* src, int dtype, long n,
+                                                          uint16_t* dst);
 void set_step(hipStream_t s, StepState* st, int kv_len, int position);
 // step state with the rotary position read on the device: round(pos[0]) of a (B, 1) position tensor
 // of dtype PGMI_DTYPE_* (+ 10 = int64, 11 = int32, 12 = float64) -- no host read of a merge's positions

@@ -4,7 +4,7 @@ The module tree, constructor signatures and state-dict names are the reference's
 (/root/reference/modeling_siglip.py:7-255), so checkpoints load unchanged.  The forward of
 SiglipVisionModel runs the whole tower in libpgmi (pgmi_vision: im2col+MFMA patch embedding,
 27 x [LayerNorm, fused QKV GEMM, MHA, out-proj+residual, LayerNorm, fc1+GELU, fc2+residual],
-post-LayerNorm; csrc/engine.hip).  The per-layer submodules (embeddings, attention, MLP, encoder
+post-LayerNorm; csrc/engine_prefill.hip).  The per-layer submodules (embeddings, attention, MLP, encoder
 layer, encoder) are callable on their own too, on libpgmi's single-op entries (pgmi/modules.py), so
 forward hooks on them fire when they are called; the fused tower does not call them.
 """

@@ -60,7 +60,7 @@ def _inv_fingerprint(inv_freq):
     return None if inv_freq is None else (inv_freq.data_ptr(), inv_freq._version, inv_freq.dtype)
 
 
-# parameters engine.prepare() builds derived tensors from (csrc/engine.hip pgmi_prepare): the text layers'
+# parameters engine.prepare() builds derived tensors from (csrc/engine_weights.hip pgmi_prepare): the text layers'
 # projections (fragment-major images read by the batched decode) and the patch embedding (its padded copy)
 _DERIVED = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
             "self_attn.o_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")

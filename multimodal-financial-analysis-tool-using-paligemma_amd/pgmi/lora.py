@@ -23,7 +23,7 @@ from typing import Dict, NamedTuple, Tuple
 import numpy as np
 
 MAX_RANK = 256
-# the Linear modules of the model: their 2-D weights are the only targets (csrc/engine.hip lora_targetable)
+# the Linear modules of the model: their 2-D weights are the only targets (csrc/engine_lora.hip lora_targetable)
 LINEAR_MODULES = ("q_proj", "k_proj", "v_proj", "o_proj", "out_proj", "gate_proj", "up_proj", "down_proj",
                   "mlp.fc1", "mlp.fc2", "multi_modal_projector.linear")
 

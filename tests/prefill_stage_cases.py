@@ -16,7 +16,7 @@ from oracle import prefill_stage_ref as R
 SEED, V, MAX_BATCH, MAX_SEQ, KV_MAX = DC.SEED, DC.V, DC.MAX_BATCH, 320, DC.KV_MAX
 KV_BATCH = DC.KV_BATCH                       # 17 > every B: a wrong batch stride lands in a visible row
 H, I, QD, KD = DC.H, DC.I, DC.QD, DC.KD
-GROUP = 8                                    # csrc/engine.hip kPrefillGroup
+GROUP = 8                                    # csrc/engine_ctx.h kPrefillGroup
 MAX_POS = DC.MAX_POS
 
 Case = namedtuple("Case", "B L kv_start lens pos kv_max")

@@ -119,7 +119,7 @@ def test_last_row_only_final_layer(eng, gold, B):
 
 @pytest.mark.parametrize("B", [1, 3])
 def test_prefill_graph_replay_matches_eager(eng, gold, B):
-    """The prefill hipGraphs (vision tower, language-model forward; engine.hip run_graphed): the
+    """The prefill hipGraphs (vision tower, language-model forward; engine_graph.h run_graphed): the
     first call with a given buffer set runs eagerly, the second captures, later ones replay.
     Every call of the sequence -- eager, capture, replay, replay after the inputs changed in
     place -- is bit-identical to an eager run with graphs switched off, and the replayed logits
@@ -133,7 +133,7 @@ def test_prefill_graph_replay_matches_eager(eng, gold, B):
     n_img = (c["v_image"] // c["v_patch"]) ** 2
     pos = torch.arange(L).expand(B, L).contiguous()             # host positions (copied per call)
     kv = eng.new_kv(B, 1024)
-    # fixed buffers: the graph key is every pointer the call reads or writes (engine.hip run_graphed)
+    # fixed buffers: the graph key is every pointer the call reads or writes (engine_graph.h run_graphed)
     vout = torch.empty((B, n_img, c["v_hidden"]), dtype=torch.bfloat16, device="cuda")
     feats = torch.empty((B, n_img, c["projection_dim"]), dtype=torch.bfloat16, device="cuda")
     logits = torch.empty((B, 1, c["t_vocab"]), dtype=torch.float32, device="cuda")
@@ -615,3 +615,34 @@ def test_graph_caches_clear_selectively(eng, gold):
     assert graph_count(eng, 1) > 0
     eng.prepare()
     assert (graph_count(eng, 0), graph_count(eng, 1)) == (0, 0)
+
+
+def test_tune_call_makes_a_new_prefill_key(eng, gold):
+    """A pgmi_tune_* call changes which kernels a prefill body launches: the tuning epoch is part of the prefill
+    key, so the next call runs eagerly under a new key instead of replaying the graph of the other plan."""
+    from pgmi import _native as N
+    c = eng.cfgd
+    n_img = (c["v_image"] // c["v_patch"]) ** 2
+    kv = eng.new_kv(1, 512)
+    L, cur, ids, pxs = _prefilled(eng, gold, 1, kv)
+    pos = torch.arange(L)[None].contiguous()
+    feats = eng.project(eng.vision(pxs))
+    logits = torch.empty((1, 1, c["t_vocab"]), dtype=torch.float32, device="cuda")
+
+    def prefill():
+        N.check(eng.lib.pgmi_lm_forward(eng.ctx, ids.data_ptr(), feats.data_ptr(), n_img, None, 1, L, pos.data_ptr(),
+                                        kv.data_ptr(), 1, kv.shape[3], 0, logits.data_ptr(), 1, eng._s()))
+
+    prefill()
+    prefill()
+    n = graph_count(eng, 0)
+    assert 0 < n <= 64
+    try:
+        N.check(eng.lib.pgmi_tune_attention(0))
+        prefill()
+        assert graph_count(eng, 0) == n + 1 <= 64
+    finally:
+        N.check(eng.lib.pgmi_tune_attention(-1))
+    prefill()
+    assert graph_count(eng, 0) == n + 2 <= 64
+    torch.cuda.synchronize()

@@ -172,3 +172,36 @@ def test_single_kernels(eng, B):
     for a, b in zip(got[P.ALL_KINDS], got[0]):
         assert torch.equal(a, b) and bool(a.float().abs().sum() > 0)
     assert not torch.equal(got[0][1], h)   # down did add to h
+
+
+@pytest.mark.parametrize("B", [1, 2])
+def test_prefill_graphs_follow_the_packed_images(eng, B):
+    """A last-row-only prefill runs the decode GEMVs, which read the 13-bit images once they exist: the step that
+    builds the images drops the prefill graphs with the small decode graphs, so the prefill key seen before runs
+    eagerly again (packed), is captured and replayed -- and gives the same logits bit for bit, the image being
+    lossless."""
+    from pgmi import _native as N
+    eng.set_decode_packed(P.ALL_KINDS)   # every kind at B = 2 as well (its default reads lm_head alone)
+    eng.prepare()                        # no images, empty caches
+    assert eng.decode_packed_info()["packed"] == 0
+    ids = _prompt(B)
+    pos = torch.arange(L0)[None].expand(B, L0).contiguous()
+    kv = torch.zeros_like(eng.new_kv(B, KV))
+    logits = torch.empty((B, 1, V), dtype=torch.float32, device="cuda")
+
+    def prefill():
+        N.check(eng.lib.pgmi_lm_forward(eng.ctx, ids.data_ptr(), None, 0, None, B, L0, pos.data_ptr(), kv.data_ptr(),
+                                        B, kv.shape[3], 0, logits.data_ptr(), 2, eng._s()))
+        torch.cuda.synchronize()
+
+    prefill()
+    first = logits.clone()
+    assert eng.lib.pgmi_graph_count(eng.ctx, 0) == 1
+    step_logits = torch.empty((B, V), dtype=torch.float32, device="cuda")
+    eng.decode(first[:, 0].argmax(-1).contiguous(), kv, L0, L0 + 1, logits=step_logits, graph=False)
+    assert eng.decode_packed_info()["packed"] == 5
+    assert eng.lib.pgmi_graph_count(eng.ctx, 0) == 0
+    for _ in range(3):   # eager, capture, replay
+        prefill()
+        assert torch.equal(logits, first)
+    assert eng.lib.pgmi_graph_count(eng.ctx, 0) == 1
