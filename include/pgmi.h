@@ -227,7 +227,7 @@ int pgmi_set_decode_staged_norm(pgmi_ctx* ctx, int on);
  *     kernel measured faster packed, all three at B = 1 and lm_head alone at B = 2 (two rows double the dot
  *     products per decoded weight: gate|up and down become VALU-limited there).  A change drops the captured decode
  *     graphs of B <= 2 and the prefill graphs (the last-row-only prefill's projections follow the setting); the
- *     batched path (B >= 3) is not touched.  Text hidden 2048 / intermediate 16384 only; other shapes stay raw.
+ *     batched path (B >= 3) is not touched (its own switch: pgmi_set_decode_packed_batched).  Text hidden 2048 / intermediate 16384 only; other shapes stay raw.
  *   - pgmi_decode_packed_info: info[0] the mask in force at B = 1 ([8]: at B = 2), [1] candidate tensors the
  *     B = 1 step reads packed now, [2] reads raw,
  *     [3] bytes of the packed ones' images, [4] bf16 bytes of the raw ones, [5] 1 if an image allocation failed
@@ -240,6 +240,29 @@ int pgmi_set_decode_staged_norm(pgmi_ctx* ctx, int on);
 int pgmi_set_decode_packed(pgmi_ctx* ctx, int on);
 int pgmi_decode_packed_info(const pgmi_ctx* ctx, int64_t* info, int n);
 int pgmi_decode_packed_tensor(const pgmi_ctx* ctx, int kind, int layer);
+/* Batched decode (3..16 rows per step): the same three kinds from a fragment-major 13-bit image.  The MFMA
+ * projections of the batched step read, per lane and 128-k block, one 52-byte record instead of four 16-byte bf16
+ * fragments, rebuild the fragments bit for bit and feed the same MFMAs in the same order: every output is identical
+ * to the bf16 launches', at any batch.  The record is the B <= 2 image's; a segment is one 16-row group x 128-k
+ * block (csrc/pack13.h), rows padded to a whole group with zeros.
+ *   - pgmi_set_decode_packed_batched: mask 0 (the default) reads the bf16 images everywhere; 1..7 is a mask of the
+ *     kinds read packed (1 gate|up, 2 down, 4 lm_head) by every step, stage hook and pgmi_decode_kernel (2, 3, 4)
+ *     with B >= 3; anything else is refused.  A change drops the captured decode graphs of B >= 3 and nothing
+ *     else; B <= 2 and the prefill (its last-row projections included, at every B) are not touched.
+ *   - The images are built like the B <= 2 ones: on the stream of the first B >= 3 step that wants them after a
+ *     pgmi_prepare, outside any capture, with one stream synchronisation, one buffer per kind; same candidates, fit
+ *     rule and shapes (hidden 2048 / intermediate 16384).  They are held beside the bf16 fragment-major images
+ *     and beside any B <= 2 images: up to 3.80 GB more at the 3B shapes with every kind on.  A kind whose buffer
+ *     cannot be allocated keeps the bf16 launches ([5]).
+ *   - pgmi_decode_packed_batched_info: info[0] the mask, [1] mask of the kinds scanned since the last pgmi_prepare,
+ *     [2] candidate tensors the batched step reads packed now, [3] reads raw, [4] bytes of the packed ones' images,
+ *     [5] 1 if an image allocation failed since the last pgmi_prepare.  n >= PGMI_PACKED_BATCHED_INFO_N.
+ *   - pgmi_decode_packed_batched_tensor: 1 if the batched step reads the tensor of `kind` (and `layer`; ignored for
+ *     lm_head) packed now, 0 if raw. */
+#define PGMI_PACKED_BATCHED_INFO_N 6
+int pgmi_set_decode_packed_batched(pgmi_ctx* ctx, int mask);
+int pgmi_decode_packed_batched_info(const pgmi_ctx* ctx, int64_t* info, int n);
+int pgmi_decode_packed_batched_tensor(const pgmi_ctx* ctx, int kind, int layer);
 /* The 13-bit format on the host (tests; no device): pgmi_pack13_scan gives e_hi and whether n bf16 values fit;
  * pgmi_pack13_bytes the image size of rows x K values (K a multiple of 2048; -1 otherwise); _encode / _decode
  * write the image and rebuild the bf16 values through the functions the kernels use. */
@@ -247,6 +270,11 @@ int pgmi_pack13_scan(const uint16_t* w, int64_t n, int* e_hi, int* fits);
 int64_t pgmi_pack13_bytes(int64_t rows, int64_t K);
 int pgmi_pack13_encode(const uint16_t* w, int64_t rows, int64_t K, int e_hi, uint8_t* image);
 int pgmi_pack13_decode(const uint8_t* image, int64_t rows, int64_t K, int e_hi, uint16_t* w);
+/* The fragment-major image of the batched step, likewise: ceil(rows / 16) * K / 128 segments of 3,328 bytes (gate|up
+ * as one 2 I x K matrix); _decode_mf writes ceil(rows / 16) * 16 rows of K values, the pad rows (+0) included. */
+int64_t pgmi_pack13_bytes_mf(int64_t rows, int64_t K);
+int pgmi_pack13_encode_mf(const uint16_t* w, int64_t rows, int64_t K, int e_hi, uint8_t* image);
+int pgmi_pack13_decode_mf(const uint8_t* image, int64_t rows, int64_t K, int e_hi, uint16_t* w);
 /* ---- LoRA adapters (the product of the reference's fine-tuning workflow, SURVEY.md C13: a peft LoraConfig on
  * q_proj / k_proj / v_proj; the PEFT helpers of modeling_gemma.py:458-466,551).  An adapter is merged into the
  * weight slab when it is activated, so the forward kernels do not change and an active adapter costs nothing per

@@ -96,12 +96,15 @@ struct TextLayerW {
     const uint16_t *mf_gate_up = nullptr, *mf_qkv = nullptr, *mf_o = nullptr, *mf_down = nullptr;
     // decode at B <= 2: the 13-bit images of gate|up and down (ensure_pk_image), img null while absent or raw
     PkW pk_gate_up, pk_down;
+    // batched decode (B >= 3): the fragment-major 13-bit images of the same two (ensure_pk_image_mf)
+    PkW pkb_gate_up, pkb_down;
 };
 struct WeightTable {
     const uint16_t *patch_conv_w, *patch_b, *pos_emb, *post_ln_w, *post_ln_b, *proj_w, *proj_b, *embed, *final_norm;
     std::vector<VisionLayerW> v;
     std::vector<TextLayerW> t;
     PkW pk_embed;  // the tied embedding's 13-bit image as lm_head reads it (the raw rows stay for look-up and prefill)
+    PkW pkb_embed;  // its fragment-major 13-bit image (the batched lm_head), rows padded to a whole 16-row group
 };
 
 // weight kinds with a 13-bit image (bits of pgmi_set_decode_packed's mask)
@@ -172,6 +175,12 @@ struct pgmi_ctx {
     unsigned* pk_stat = nullptr;
     int pk_mask = -1, pk_done = 0;
     bool pk_alloc_failed = false;
+    // batched decode (B >= 3): the fragment-major 13-bit images of the same tensors (pack13.h), buffers of their
+    // own; pk_mask_batched: the kinds the batched step reads packed (pgmi_set_decode_packed_batched, default none);
+    // pk_done_batched: as pk_done.  Built by ensure_pk_image_mf, read through w.t[i].pkb_* / w.pkb_embed
+    uint8_t* pkb_buf[3] = {nullptr, nullptr, nullptr};
+    int pk_mask_batched = 0, pk_done_batched = 0;
+    bool pkb_alloc_failed = false;
     float *opart, *pmax, *dlogits, *amax_v;
     int *pidx, *amax_i;
     int max_chunks;
@@ -218,10 +227,13 @@ inline int pk_mask_for(const pgmi_ctx* x, int B) {
     return x->pk_mask >= 0 ? x->pk_mask : B <= 1 ? kPkDefaultB1 : kPkDefaultB2;
 }
 
-// the image a B-row streaming GEMV of `kind` reads now: w, or none (the bf16 rows) while the kind is switched
-// off, not built since the last pgmi_prepare, or the tensor did not fit (w.img null)
-inline PkW pk_use(const pgmi_ctx* x, int B, int kind, const PkW& w) {
-    const bool on = B <= 2 && B < gemv_mf_min_batch() && (pk_mask_for(x, B) & x->pk_done & kind);
+// the image a B-row decode GEMV of `kind` reads now: w (B <= 2, the streaming forms) or *wb (B >= 3, the MFMA
+// forms' fragment-major image), or none (the bf16 weights) while the kind is switched off for that batch, not
+// built since the last pgmi_prepare, or the tensor did not fit (img null).  wb null: the caller has no batched
+// packed form (the prefill's last-row GEMVs launch at B >= 3 what they always did).
+inline PkW pk_use(const pgmi_ctx* x, int B, int kind, const PkW& w, const PkW* wb = nullptr) {
+    if (B >= gemv_mf_min_batch()) return wb && (x->pk_mask_batched & x->pk_done_batched & kind) ? *wb : PkW{};
+    const bool on = B <= 2 && (pk_mask_for(x, B) & x->pk_done & kind);
     return on ? w : PkW{};
 }
 
@@ -285,6 +297,7 @@ void pk_forget(pgmi_ctx* x);
 void pk_forget_kinds(pgmi_ctx* x, int kinds);
 int ensure_mf_image(pgmi_ctx* x, hipStream_t s);
 int ensure_pk_image(pgmi_ctx* x, hipStream_t s, int B);
+int ensure_pk_image_mf(pgmi_ctx* x, hipStream_t s);
 // engine_lora.hip
 void lora_forget_pristine(pgmi_ctx* x);
 // engine_prefill.hip: what a prefill does before its launches, then the stages of one row group (PrefillRun) --

@@ -25,6 +25,10 @@
 //      pk_done                   pk_forget <- pgmi_bind_weights, pgmi_prepare             all
 //                                pk_forget_kinds <- pgmi_lora_set                         decode B <= 2, prefill
 //      pk_mask                   pgmi_set_decode_packed                                   decode B <= 2, prefill
+//      w.t[i].pkb_*, w.pkb_embed, ensure_pk_image_mf, when it changed pk_done_batched     decode B >= 3
+//      pk_done_batched           pk_forget <- pgmi_bind_weights, pgmi_prepare             all
+//                                pk_forget_kinds <- pgmi_lora_set (gate / up / down)      decode B >= 3
+//      pk_mask_batched           pgmi_set_decode_packed_batched                           decode B >= 3
 //      mf_staged                 pgmi_set_decode_staged_norm                              decode, small and batched
 //      probe_on, probe_ev        pgmi_prefill_probe (prefill graphs are off while on)     prefill
 //      prefill_graph             pgmi_set_prefill_graph, pgmi_prefill_probe               prefill

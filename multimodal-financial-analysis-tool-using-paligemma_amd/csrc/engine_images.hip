@@ -1,27 +1,29 @@
 // engine_images.hip -- libpgmi host side: the weight images the decode step reads instead of the slab's rows --
-// fragment-major (B >= 3, kernels_gemv_mfma.hip) and 13-bit (B <= 2, pack13.h) -- built on demand by the first
-// step that wants them, their switch and info calls, and the 13-bit format on the host.
+// fragment-major (B >= 3, kernels_gemv_mfma.hip) and 13-bit (pack13.h: row-major segments for B <= 2, fragment-major
+// ones for B >= 3) -- built on demand by the first step that wants them, their switch and info calls, and the
+// 13-bit format on the host.
 #include "engine_graph.h"
 
 namespace pgmi_eng __attribute__((visibility("hidden"))) {
 
 // the weights changed (pgmi_prepare, a new slab): no image is valid until ensure_pk_image has rebuilt it
 void pk_forget(pgmi_ctx* x) {
-    x->pk_done = 0;
-    x->pk_alloc_failed = false;
-    x->w.pk_embed = PkW{};
-    for (auto& t : x->w.t) t.pk_gate_up = t.pk_down = PkW{};
+    x->pk_done = x->pk_done_batched = 0;
+    x->pk_alloc_failed = x->pkb_alloc_failed = false;
+    x->w.pk_embed = x->w.pkb_embed = PkW{};
+    for (auto& t : x->w.t) t.pk_gate_up = t.pk_down = t.pkb_gate_up = t.pkb_down = PkW{};
 }
 
-// forget the 13-bit images of the kinds in `kinds` alone (their tensors changed): the next B <= 2 step rescans
-// and repacks those, the other kinds' images stay
+// forget the 13-bit images of the kinds in `kinds` alone (their tensors changed), row-major and fragment-major: the
+// next step that wants them rescans and repacks those, the other kinds' images stay
 void pk_forget_kinds(pgmi_ctx* x, int kinds) {
     x->pk_done &= ~kinds;
+    x->pk_done_batched &= ~kinds;
     for (auto& t : x->w.t) {
-        if (kinds & PK_GATE_UP) t.pk_gate_up = PkW{};
-        if (kinds & PK_DOWN) t.pk_down = PkW{};
+        if (kinds & PK_GATE_UP) t.pk_gate_up = t.pkb_gate_up = PkW{};
+        if (kinds & PK_DOWN) t.pk_down = t.pkb_down = PkW{};
     }
-    if (kinds & PK_LM_HEAD) x->w.pk_embed = PkW{};
+    if (kinds & PK_LM_HEAD) x->w.pk_embed = x->w.pkb_embed = PkW{};
 }
 
 // The fragment-major images of every layer's gate|up, q|k|v, o_proj and down weights that the batched (B >= 3)
@@ -60,21 +62,22 @@ int ensure_mf_image(pgmi_ctx* x, hipStream_t s) {
     return 0;
 }
 
+// the PK kernels are the K = 2048 / K = 16384 forms: other shapes stay raw
+static bool pk_shapes(const pgmi_config& c) { return c.t_hidden == 2048 && c.t_intermediate == 16384; }
+
 // The 13-bit images (pack13.h) that the streaming GEMVs of the B <= 2 decode step read instead of the bf16 rows:
 // every layer's gate|up (one 2 I x H tensor) and down, and the tied embedding as lm_head reads it -- 2 L + 1
 // candidate tensors, 13/16 of their bytes (3.80 GB beside the resident bf16 weights at the 3B shapes).  (Re)built
 // on stream s by the first such step after a pgmi_prepare, outside any capture: pass one scans each tensor's
 // exponent range, the host reads the 2 L + 1 results (one stream synchronisation) and packs the tensors that fit;
 // a tensor that does not fit keeps the bf16 kernel, as does a whole kind whose buffer cannot be allocated.
-int ensure_pk_image(pgmi_ctx* x, hipStream_t s, int B) {
-    const int want = pk_mask_for(x, B) & ~x->pk_done;
-    if (!want) return 0;
+//
+// mf: the fragment-major images of the batched (B >= 3) step instead (ensure_pk_image_mf) -- the same candidates,
+// scan and fit rule, pk_pack_mf's gather, buffers and PkW entries of their own (pkb_*), lm_head's rows padded to a
+// whole group.  settled: the kinds now scanned, or given up for this weight set; 0 inside a capture.
+static int pk_build(pgmi_ctx* x, hipStream_t s, int want, bool mf, int* settled) {
+    *settled = 0;
     const pgmi_config& c = x->c;
-    // the PK kernels are the K = 2048 / K = 16384 forms
-    if (c.t_hidden != 2048 || c.t_intermediate != 16384) {
-        x->pk_done |= want;
-        return 0;
-    }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
         (void)hipGetLastError();
@@ -84,29 +87,32 @@ int ensure_pk_image(pgmi_ctx* x, hipStream_t s, int B) {
     const int64_t I = c.t_intermediate, H = c.t_hidden, V = c.t_vocab;
     struct Cand { int kind; const uint16_t* W; int64_t rows, K; PkW* dst; uint8_t* out; };
     std::vector<Cand> cands;
-    const int64_t gu_b = pk_image_bytes(2 * I, H), dn_b = pk_image_bytes(H, I), em_b = pk_image_bytes(V, H);
+    const auto bytes = [mf](int64_t rows, int64_t K) { return mf ? pk_image_bytes_mf(rows, K) : pk_image_bytes(rows, K); };
+    const int64_t gu_b = bytes(2 * I, H), dn_b = bytes(H, I), em_b = bytes(V, H);
     const int64_t kind_bytes[3] = {gu_b * L, dn_b * L, em_b};
+    uint8_t** bufs = mf ? x->pkb_buf : x->pk_buf;
     int got = 0;
     for (int k = 0; k < 3; ++k) {
         if (!(want & (1 << k)) || kind_bytes[k] == 0) continue;
-        if (!x->pk_buf[k]) {
+        if (!bufs[k]) {
             void* p = nullptr;
             if (hipMalloc(&p, (size_t)kind_bytes[k]) != hipSuccess) {
                 (void)hipGetLastError();  // out of memory: this kind keeps the bf16 kernels
-                x->pk_alloc_failed = true;
+                (mf ? x->pkb_alloc_failed : x->pk_alloc_failed) = true;
                 continue;
             }
             x->allocs.push_back(p);
-            x->pk_buf[k] = reinterpret_cast<uint8_t*>(p);
+            bufs[k] = reinterpret_cast<uint8_t*>(p);
         }
         got |= 1 << k;
     }
     for (int i = 0; i < L; ++i) {
         TextLayerW& w = x->w.t[i];
-        if (got & PK_GATE_UP) cands.push_back({PK_GATE_UP, w.gate_up, 2 * I, H, &w.pk_gate_up, x->pk_buf[0] + gu_b * i});
-        if (got & PK_DOWN) cands.push_back({PK_DOWN, w.down, H, I, &w.pk_down, x->pk_buf[1] + dn_b * i});
+        if (got & PK_GATE_UP)
+            cands.push_back({PK_GATE_UP, w.gate_up, 2 * I, H, mf ? &w.pkb_gate_up : &w.pk_gate_up, bufs[0] + gu_b * i});
+        if (got & PK_DOWN) cands.push_back({PK_DOWN, w.down, H, I, mf ? &w.pkb_down : &w.pk_down, bufs[1] + dn_b * i});
     }
-    if (got & PK_LM_HEAD) cands.push_back({PK_LM_HEAD, x->w.embed, V, H, &x->w.pk_embed, x->pk_buf[2]});
+    if (got & PK_LM_HEAD) cands.push_back({PK_LM_HEAD, x->w.embed, V, H, mf ? &x->w.pkb_embed : &x->w.pk_embed, bufs[2]});
     if (!cands.empty()) {
         const size_t n = cands.size(), cap_n = (size_t)2 * L + 1;
         if (!x->pk_stat) {
@@ -130,16 +136,50 @@ int ensure_pk_image(pgmi_ctx* x, hipStream_t s, int B) {
                 *cands[t].dst = PkW{};
                 continue;
             }
-            pk_pack(s, cands[t].W, (long)cands[t].rows, (int)cands[t].K, e_hi, cands[t].out);
+            if (mf) pk_pack_mf(s, cands[t].W, (long)cands[t].rows, (int)cands[t].K, e_hi, cands[t].out);
+            else pk_pack(s, cands[t].W, (long)cands[t].rows, (int)cands[t].K, e_hi, cands[t].out);
             cands[t].dst->img = cands[t].out;
             cands[t].dst->base2 = pk_base2(e_hi);
         }
         LAUNCHCHK();
     }
-    x->pk_done |= want;
+    *settled = want;
+    return 0;
+}
+
+int ensure_pk_image(pgmi_ctx* x, hipStream_t s, int B) {
+    const int want = pk_mask_for(x, B) & ~x->pk_done;
+    if (!want) return 0;
+    if (!pk_shapes(x->c)) {
+        x->pk_done |= want;
+        return 0;
+    }
+    int settled = 0;
+    if (int rc = pk_build(x, s, want, false, &settled)) return rc;
+    if (!settled) return 0;
+    x->pk_done |= settled;
     // steps captured before held the bf16 launches, and so did a prefill's last-row GEMVs (lm_last_row_tail,
     // lm_logits: pk_use reads pk_done); a prefill key merely seen before runs eagerly again, in the packed form
     graphs_drop(x, GRAPHS_DECODE_SMALL | GRAPHS_PREFILL);
+    return 0;
+}
+
+// The fragment-major 13-bit images the batched step's gate|up, down and lm_head launches read under
+// pgmi_set_decode_packed_batched: built like the B <= 2 ones (pk_build), by the first B >= 3 step that wants them
+// after a pgmi_prepare.  The bf16 fragment-major image mfw stays: a B >= 3 engine with every kind on holds both
+// (up to 3.80 GB more at the 3B shapes).  The prefill never reads these (pk_use: its last-row GEMVs pass none).
+int ensure_pk_image_mf(pgmi_ctx* x, hipStream_t s) {
+    const int want = x->pk_mask_batched & ~x->pk_done_batched;
+    if (!want) return 0;
+    if (!pk_shapes(x->c)) {
+        x->pk_done_batched |= want;
+        return 0;
+    }
+    int settled = 0;
+    if (int rc = pk_build(x, s, want, true, &settled)) return rc;
+    if (!settled) return 0;
+    x->pk_done_batched |= settled;
+    graphs_drop(x, GRAPHS_DECODE_BATCHED);  // steps captured before held the bf16 launches
     return 0;
 }
 
@@ -154,6 +194,45 @@ int pgmi_set_decode_packed(pgmi_ctx* x, int on) {
     // captured steps hold the other form's launches (a last-row-only prefill's GEMVs follow the setting)
     graphs_drop(x, GRAPHS_DECODE_SMALL | GRAPHS_PREFILL);
     return 0;
+}
+
+int pgmi_set_decode_packed_batched(pgmi_ctx* x, int mask) {
+    if (!x) return fail(PGMI_E_ARG, "null context");
+    if (mask < 0 || mask > PK_ALL)
+        return fail(PGMI_E_ARG, "decode_packed_batched: 0 off, 1..7 a mask of kinds (1 gate|up, 2 down, 4 lm_head)");
+    x->pk_mask_batched = mask;
+    graphs_drop(x, GRAPHS_DECODE_BATCHED);  // captured B >= 3 steps hold the other form's launches
+    return 0;
+}
+
+int pgmi_decode_packed_batched_info(const pgmi_ctx* x, int64_t* info, int n) {
+    if (!x || !info) return fail(PGMI_E_ARG, "null argument");
+    if (n < PGMI_PACKED_BATCHED_INFO_N) return fail(PGMI_E_ARG, "info needs PGMI_PACKED_BATCHED_INFO_N entries");
+    const pgmi_config& c = x->c;
+    const int64_t I = c.t_intermediate, H = c.t_hidden, V = c.t_vocab;
+    const bool shapes = H == 2048 && I == 16384;
+    const int on = x->pk_mask_batched & x->pk_done_batched;
+    int64_t np = 0, nr = 0, bp = 0;
+    auto count = [&](int kind, const PkW& w, int64_t rows, int64_t K) {
+        if ((on & kind) && w.img && shapes) { ++np; bp += pk_image_bytes_mf(rows, K); }
+        else ++nr;
+    };
+    for (size_t i = 0; i < x->w.t.size(); ++i) {
+        count(PK_GATE_UP, x->w.t[i].pkb_gate_up, 2 * I, H);
+        count(PK_DOWN, x->w.t[i].pkb_down, H, I);
+    }
+    count(PK_LM_HEAD, x->w.pkb_embed, V, H);
+    info[0] = x->pk_mask_batched; info[1] = x->pk_done_batched; info[2] = np; info[3] = nr; info[4] = bp;
+    info[5] = x->pkb_alloc_failed;
+    return 0;
+}
+
+int pgmi_decode_packed_batched_tensor(const pgmi_ctx* x, int kind, int layer) {
+    if (!x) return fail(PGMI_E_ARG, "null context");
+    if (kind != PK_GATE_UP && kind != PK_DOWN && kind != PK_LM_HEAD) return fail(PGMI_E_ARG, "kind: 1 gate|up, 2 down, 4 lm_head");
+    if (kind != PK_LM_HEAD && (layer < 0 || layer >= (int)x->w.t.size())) return fail(PGMI_E_ARG, "layer out of range");
+    const PkW& w = kind == PK_LM_HEAD ? x->w.pkb_embed : kind == PK_GATE_UP ? x->w.t[layer].pkb_gate_up : x->w.t[layer].pkb_down;
+    return (x->pk_mask_batched & x->pk_done_batched & kind) && w.img ? 1 : 0;
 }
 
 int pgmi_decode_packed_info(const pgmi_ctx* x, int64_t* info, int n) {
@@ -244,6 +323,59 @@ int pgmi_pack13_decode(const uint8_t* image, int64_t rows, int64_t K, int e_hi, 
                 std::memcpy(w + seg * kPkSegK + 512 * ch + 8 * l, &f, 16);
             }
         }
+    return 0;
+}
+
+// The fragment-major gather (the batched step's image): ceil(rows / 16) x K / 128 segments, rows past the last
+// encoded as zeros.
+int64_t pgmi_pack13_bytes_mf(int64_t rows, int64_t K) {
+    if (rows < 1 || K < kPkSegK || K % kPkSegK != 0) return -1;
+    return pk_image_bytes_mf(rows, K);
+}
+
+int pgmi_pack13_encode_mf(const uint16_t* w, int64_t rows, int64_t K, int e_hi, uint8_t* image) {
+    if (!w || !image) return fail(PGMI_E_ARG, "null argument");
+    if (pgmi_pack13_bytes_mf(rows, K) < 0) return fail(PGMI_E_ARG, "pack13: K must be a positive multiple of 2048, rows >= 1");
+    if (e_hi < 0 || e_hi > 255) return fail(PGMI_E_ARG, "pack13: e_hi is an exponent field (0..255)");
+    for (int64_t gr = 0; gr < pk_mf_groups(rows); ++gr)
+        for (int64_t kb = 0; kb < K / kPkMfK; ++kb)
+            for (int l = 0; l < 64; ++l) {
+                uint4 f[4];
+                const int64_t row = pk_mf_row(gr, l);
+                for (int ch = 0; ch < 4; ++ch) {
+                    if (row < rows) std::memcpy(&f[ch], w + row * K + pk_mf_k(kb, l, ch), 16);
+                    else f[ch] = make_uint4(0, 0, 0, 0);
+                }
+                const PkSeg sg = pk_encode(f, e_hi);
+                uint8_t* d = image + pk_mf_seg(gr, kb, K) * kPkSegBytes;
+                std::memcpy(d + pk_off_a(l), &sg.a, 16);
+                std::memcpy(d + pk_off_b(l), &sg.b, 16);
+                std::memcpy(d + pk_off_n(l), &sg.n, 16);
+                std::memcpy(d + pk_off_h(l), &sg.h, 4);
+            }
+    return 0;
+}
+
+// w: pk_mf_groups(rows) * 16 rows of K values (the pad rows included: they decode to +0)
+int pgmi_pack13_decode_mf(const uint8_t* image, int64_t rows, int64_t K, int e_hi, uint16_t* w) {
+    if (!w || !image) return fail(PGMI_E_ARG, "null argument");
+    if (pgmi_pack13_bytes_mf(rows, K) < 0) return fail(PGMI_E_ARG, "pack13: K must be a positive multiple of 2048, rows >= 1");
+    if (e_hi < 0 || e_hi > 255) return fail(PGMI_E_ARG, "pack13: e_hi is an exponent field (0..255)");
+    const unsigned b2 = pk_base2(e_hi);
+    for (int64_t gr = 0; gr < pk_mf_groups(rows); ++gr)
+        for (int64_t kb = 0; kb < K / kPkMfK; ++kb)
+            for (int l = 0; l < 64; ++l) {
+                const uint8_t* d = pk_host_seg(image, pk_mf_seg(gr, kb, K));
+                PkSeg sg;
+                std::memcpy(&sg.a, d + pk_off_a(l), 16);
+                std::memcpy(&sg.b, d + pk_off_b(l), 16);
+                std::memcpy(&sg.n, d + pk_off_n(l), 16);
+                std::memcpy(&sg.h, d + pk_off_h(l), 4);
+                for (int ch = 0; ch < 4; ++ch) {
+                    const uint4 f = pk_chunk(sg, ch, b2);
+                    std::memcpy(w + pk_mf_row(gr, l) * K + pk_mf_k(kb, l, ch), &f, 16);
+                }
+            }
     return 0;
 }
 

@@ -94,6 +94,7 @@ void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W,
     GemvArgs a{};
     a.x = x; a.norm_w = nullptr; a.W = W; a.n_units = N; a.K = K; a.nb = B; a.out = h_inout;
     if (B >= gemv_mf_min_batch() && K % 128 == 0 && ws) {
+        if (K == 16384 && N % 16 == 0) { a.Wp = pk.img; a.pk_base2 = pk.base2; }  // the fragment-major 13-bit image
         gemv_mf_res(s, a, ws);
         return;
     }
@@ -127,15 +128,16 @@ void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W,
 // batched (MFMA) residual projection whose combine also writes the next RMSNorm of h (hn); other
 // batches / shapes: gemv_res, then rows_norm
 void gemv_res_norm(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W, int N, uint16_t* h_inout,
-                   float* ws, const uint16_t* norm_w, float eps, uint16_t* hn, const uint16_t* Wf) {
+                   float* ws, const uint16_t* norm_w, float eps, uint16_t* hn, const uint16_t* Wf, PkW pk) {
     if (B >= gemv_mf_min_batch() && K % 2048 == 0 && K / 2048 <= 8 && K > 2048 && ws) {
         GemvArgs a{};
         a.x = x; a.norm_w = nullptr; a.W = W; a.n_units = N; a.K = K; a.nb = B; a.out = h_inout;
         a.Wf = N % 16 == 0 ? Wf : nullptr;
+        if (K == 16384 && N % 16 == 0) { a.Wp = pk.img; a.pk_base2 = pk.base2; }
         gemv_mf_res_norm(s, a, ws, norm_w, eps, hn);
         return;
     }
-    gemv_res(s, B, K, x, W, N, h_inout, ws);
+    gemv_res(s, B, K, x, W, N, h_inout, ws, pk);
     if (norm_w) rows_norm(s, h_inout, norm_w, eps, B, N, hn);
 }
 
@@ -170,6 +172,7 @@ void gemv_geglu(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w,
     if (B >= gemv_mf_min_batch()) {
         a.ssq = norm_w ? ssq : nullptr;
         a.Wf = I % 16 == 0 ? Wf : nullptr;
+        if (I % 16 == 0) { a.Wp = pk.img; a.pk_base2 = pk.base2; }  // the fragment-major 13-bit image
         gemv_mf_geglu(s, a);
         return;
     }
@@ -192,6 +195,7 @@ bool gemv_logits(hipStream_t s, int B, const uint16_t* h, const uint16_t* norm_w
     const int mb = gemv_logits_blocks();  // pmax/pidx capacity
     int blocks;
     if (B >= gemv_mf_min_batch()) {
+        a.Wp = pk.img; a.pk_base2 = pk.base2;  // the fragment-major 13-bit image
         *nparts = gemv_mf_logits(s, a, mb);
         return false;
     }

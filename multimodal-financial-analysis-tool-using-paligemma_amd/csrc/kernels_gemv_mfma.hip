@@ -144,9 +144,16 @@ void mf_swizzle(hipStream_t s, const uint16_t* W, int rows, int K, uint16_t* out
 #endif
 // RG (GV_QKV): the ragged step -- batch row b takes its RoPE row and KV-append row from its own step record
 // st[b * st_stride]; RG = false reads record 0 once for every row (the lock-step kernels, unchanged)
-template <int MODE, int NR, int KW, int WK, int PF = 1, bool NS = false, bool SW = false, bool RG = false>
+// PK (gate|up, down): the weights come from the fragment-major 13-bit image a.Wp (pack13.h: one segment per 16-row
+// group x 128-k block, 52 instead of 64 bytes per lane and k block); each B fragment is rebuilt bit for bit
+// (pk_chunk) right before its MFMA, which are the bf16 kernel's in the bf16 kernel's order -- so is every output.
+// The VALU that rebuilds them is otherwise idle while the wave waits for its stream.
+template <int MODE, int NR, int KW, int WK, int PF = 1, bool NS = false, bool SW = false, bool RG = false,
+          bool PK = false>
 __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restrict__ ws) {
     static_assert(!RG || MODE == GV_QKV, "per-row step records: q|k|v only");
+    static_assert(!PK || ((MODE == GV_GEGLU || MODE == GV_RES) && PF == 1 && !SW),
+                  "13-bit image: gate|up and down, one-deep streams, its own addressing");
     constexpr int NKB = KW / 128;          // 128-wide k blocks per wave
     constexpr bool STAGE = (MODE != GV_RES) && !NS;
     // (the fragment-major image, SW: every load reads whole lines once -- non-temporal)
@@ -174,24 +181,44 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
         else if constexpr (MODE == GV_GEGLU) return (long)u + (long)j * a.I;
         else return (long)u;
     };
-    uint4 w[NR][NKB][4];
+    uint4 w[PK ? 1 : NR][PK ? 1 : NKB][4];
+    PkSeg wp[PK ? NR : 1][PK ? NKB : 1];
     // SW: the fragment-major image (k_mf_swizzle; n_units % 16 == 0, the up rows' image of n_groups groups
     // after the gate rows'): lane-linear 1-KiB pieces, k block stride 512 elements, read non-temporal
     static_assert(!SW || PF == 1, "fragment-major image: one-deep register streams");
     auto issue = [&](int grp) {
-        int u = grp * 16 + n;
-        if (u >= a.n_units) u = a.n_units - 1;  // clamp: duplicate row, result discarded
+        if constexpr (PK) {
+            // this wave's NKB segments of group grp (of row set j): each of a lane's four loads is one piece of a
+            // contiguous, 128-byte-aligned run of the wave, whole lines read once -- non-temporal.  The image holds
+            // every group to its 16th row (zeros past the last), so no row is clamped
 #pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const uint16_t* rp = SW ? a.W + (((long)j * n_groups + grp) * (K / 32) + k0 / 32) * 512 + lane * 8
-                                    : a.W + row_of(u, j) * K + k0 + 8 * g;
+            for (int j = 0; j < NR; ++j) {
+                const uint8_t* sp = a.Wp + pk_mf_seg((long)j * n_groups + grp, k0 / kPkMfK, K) * (long)kPkSegBytes;
 #pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const long o = SW ? (long)(kb * 4 + i) * 512 : kb * 128 + 32 * i;
-                    w[j][kb][i] = kNt ? ldg_nt(rp + o) : ldg16(rp + o);
+                for (int kb = 0; kb < NKB; ++kb) {
+                    const uint8_t* q = sp + kb * kPkSegBytes;
+                    PkSeg& d = wp[j][kb];
+                    d.a = ldg_nt(q + pk_off_a(lane));
+                    d.b = ldg_nt(q + pk_off_b(lane));
+                    d.n = ldg_nt(q + pk_off_n(lane));
+                    d.h = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(q + pk_off_h(lane)));
                 }
+            }
+        } else {
+            int u = grp * 16 + n;
+            if (u >= a.n_units) u = a.n_units - 1;  // clamp: duplicate row, result discarded
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+                const uint16_t* rp = SW ? a.W + (((long)j * n_groups + grp) * (K / 32) + k0 / 32) * 512 + lane * 8
+                                        : a.W + row_of(u, j) * K + k0 + 8 * g;
+#pragma unroll
+                for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const long o = SW ? (long)(kb * 4 + i) * 512 : kb * 128 + 32 * i;
+                        w[j][kb][i] = kNt ? ldg_nt(rp + o) : ldg16(rp + o);
+                    }
+            }
         }
     };
     if constexpr (PF == 2) {
@@ -375,7 +402,11 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) acc[j] = mfma16(xf[kb][i], __builtin_bit_cast(short8, w[j][kb][i]), acc[j]);
+                for (int i = 0; i < 4; ++i) {
+                    if constexpr (PK)
+                        acc[j] = mfma16(xf[kb][i], __builtin_bit_cast(short8, pk_chunk(wp[j][kb], i, a.pk_base2)), acc[j]);
+                    else acc[j] = mfma16(xf[kb][i], __builtin_bit_cast(short8, w[j][kb][i]), acc[j]);
+                }
         }
         const int cur = grp;
         if constexpr (NEXT) issue(grp + gridDim.x);  // the next group's stream starts now (it exists)
@@ -522,10 +553,15 @@ __device__ __forceinline__ void mf_vmcnt() {
 #ifndef PGMI_ML_AUX
 #define PGMI_ML_AUX 2
 #endif
-template <int MODE, int NR, int KSL, int D>
+// PK: the ring carries the fragment-major 13-bit image a.Wp (pack13.h) instead -- a k block of the wave's 16 rows
+// is one 3,328-byte segment, whose four pieces (three lane-linear 1-KiB runs and one of 256 B) are what four
+// LDS-DMA instructions write as they are; each lane then reads its own record back (lane-linear: conflict-free)
+// and rebuilds its four B fragments (pk_chunk) for the same MFMAs in the same order.  Same instruction count per
+// k block, so the ring's vmcnt bookkeeping is the bf16 form's; a slot is 13/16 of its bytes.
+template <int MODE, int NR, int KSL, int D, bool PK = false>
 __global__ void __launch_bounds__(256, 1) k_gemv_ml(GemvArgs a, float* __restrict__ ws) {
     constexpr int NKB = KSL / 128;
-    constexpr int SLOT = NR * 16 * 256;  // bytes of one k block of the wave's rows
+    constexpr int SLOT = PK ? NR * kPkSegBytes : NR * 16 * 256;  // bytes of one k block of the wave's rows
     constexpr int PER = NR * 4;          // LDS-DMA instructions per k block
     static_assert((D - 1) * PER <= 63, "ring shape");
     extern __shared__ __attribute__((aligned(16))) uint8_t mls[];
@@ -554,16 +590,33 @@ __global__ void __launch_bounds__(256, 1) k_gemv_ml(GemvArgs a, float* __restric
     auto issue = [&](int grp, int kb, int slot) {
         kb += rot_of(grp);
         if (kb >= NKB) kb -= NKB;
+        if constexpr (PK) {
+            // (the image holds every group to its 16th row: nothing to clamp)
 #pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = q / 4, r = 4 * (q % 4) + prow;
-            int u = grp * 16 + r;
-            if (u >= a.n_units) u = a.n_units - 1;
-            const int c = ppos ^ r;  // source chunk landing at position ppos of row r
-            const uint16_t* src = a.W + row_of(u, j) * K + k0 + kb * 128 + c * 8;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src),
-                                             (__attribute__((address_space(3))) void*)(ring + slot * SLOT + q * 1024), 16, 0,
-                                             PGMI_ML_AUX);
+            for (int j = 0; j < NR; ++j) {
+                const uint8_t* sp = a.Wp + pk_mf_seg((long)j * n_groups + grp, k0 / kPkMfK + kb, K) * (long)kPkSegBytes;
+                uint8_t* dp = ring + slot * SLOT + j * kPkSegBytes;
+                __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(sp + pk_off_a(lane)),
+                                                 (__attribute__((address_space(3))) void*)(dp + pk_off_a(0)), 16, 0, PGMI_ML_AUX);
+                __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(sp + pk_off_b(lane)),
+                                                 (__attribute__((address_space(3))) void*)(dp + pk_off_b(0)), 16, 0, PGMI_ML_AUX);
+                __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(sp + pk_off_n(lane)),
+                                                 (__attribute__((address_space(3))) void*)(dp + pk_off_n(0)), 16, 0, PGMI_ML_AUX);
+                __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(sp + pk_off_h(lane)),
+                                                 (__attribute__((address_space(3))) void*)(dp + pk_off_h(0)), 4, 0, PGMI_ML_AUX);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < PER; ++q) {
+                const int j = q / 4, r = 4 * (q % 4) + prow;
+                int u = grp * 16 + r;
+                if (u >= a.n_units) u = a.n_units - 1;
+                const int c = ppos ^ r;  // source chunk landing at position ppos of row r
+                const uint16_t* src = a.W + row_of(u, j) * K + k0 + kb * 128 + c * 8;
+                __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src),
+                                                 (__attribute__((address_space(3))) void*)(ring + slot * SLOT + q * 1024), 16,
+                                                 0, PGMI_ML_AUX);
+            }
         }
     };
     int grp = blockIdx.x * wpb + wave;
@@ -612,13 +665,23 @@ __global__ void __launch_bounds__(256, 1) k_gemv_ml(GemvArgs a, float* __restric
             // block kb landed: the younger D-1 blocks may still be in flight (only while they exist)
             if (kb + D <= NKB || more) mf_vmcnt<(D - 1) * PER>();
             else mf_vmcnt<0>();
-            const uint8_t* sb = ring + slot * SLOT + n * 256;
+            const uint8_t* sb = ring + slot * SLOT + (PK ? 0 : n * 256);
             short8 wf[NR][4];
+            PkSeg ps[PK ? NR : 1];
 #pragma unroll
-            for (int j = 0; j < NR; ++j)
+            for (int j = 0; j < NR; ++j) {
+                if constexpr (PK) {
+                    const uint8_t* q = sb + j * kPkSegBytes;
+                    ps[j].a = *reinterpret_cast<const uint4*>(q + pk_off_a(lane));
+                    ps[j].b = *reinterpret_cast<const uint4*>(q + pk_off_b(lane));
+                    ps[j].n = *reinterpret_cast<const uint4*>(q + pk_off_n(lane));
+                    ps[j].h = *reinterpret_cast<const unsigned*>(q + pk_off_h(lane));
+                } else {
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    wf[j][i] = *reinterpret_cast<const short8*>(sb + j * 4096 + (((4 * i + g) ^ n) << 4));
+                    for (int i = 0; i < 4; ++i)
+                        wf[j][i] = *reinterpret_cast<const short8*>(sb + j * 4096 + (((4 * i + g) ^ n) << 4));
+                }
+            }
             short8 xv[4];
             const int kr = kb + rot < NKB ? kb + rot : kb + rot - NKB;
 #pragma unroll
@@ -629,6 +692,12 @@ __global__ void __launch_bounds__(256, 1) k_gemv_ml(GemvArgs a, float* __restric
             __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the slot's reads are done
             if (kb + D < NKB) issue(grp, kb + D, slot);
             else if (more) issue(nxt, kb + D - NKB, slot);
+            if constexpr (PK) {  // the slot's record is in registers (lgkmcnt(0) above): rebuild the fragments
+#pragma unroll
+                for (int j = 0; j < NR; ++j)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) wf[j][i] = __builtin_bit_cast(short8, pk_chunk(ps[j], i, a.pk_base2));
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -853,12 +922,13 @@ void rows_norm(hipStream_t s, const uint16_t* x, const uint16_t* w, float eps, i
 // smallest lock-step batch whose decode projections run on MFMA (B <= 2: the v_dot2 GEMVs of gemv_body.h)
 int gemv_mf_min_batch() { return 3; }
 
-template <int MODE, int NR, int KW, int WK, int PF = 1, bool NS = false, bool SW = false, bool RG = false>
+template <int MODE, int NR, int KW, int WK, int PF = 1, bool NS = false, bool SW = false, bool RG = false,
+          bool PK = false>
 static void launch_mf(hipStream_t s, const GemvArgs& a, int blocks, int KS, float* ws) {
     const size_t lds = (MODE == GV_RES || NS) ? 0 : (size_t)a.nb * (a.K + 8) * sizeof(uint16_t);
     static size_t attr = 0;
     if (lds > attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG, PK>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {  // not launched: the engine reports it with its launch errors
             launch_error_set(e, "k_gemv_mf: dynamic LDS size");
@@ -866,18 +936,19 @@ static void launch_mf(hipStream_t s, const GemvArgs& a, int blocks, int KS, floa
         }
         attr = lds;
     }
-    hipLaunchKernelGGL((k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG>), dim3(blocks, KS), dim3(64 * WK), lds, s, a, ws);
+    hipLaunchKernelGGL((k_gemv_mf<MODE, NR, KW, WK, PF, NS, SW, RG, PK>), dim3(blocks, KS), dim3(64 * WK), lds, s, a, ws);
 }
 
 static int groups_of(int units) { return (units + 15) / 16; }
 
 // waves: streaming waves per workgroup (GV_LOGITS keeps 4: its block reduction is laid out for 4 waves)
-template <int MODE, int NR, int KSL, int D>
+template <int MODE, int NR, int KSL, int D, bool PK = false>
 static void launch_ml(hipStream_t s, const GemvArgs& a, int blocks, int KS, float* ws, int waves = 4) {
-    const size_t lds = (((size_t)a.nb * (KSL + 8) * 2 + 127) & ~(size_t)127) + (size_t)waves * D * NR * 16 * 256;
+    const size_t lds = (((size_t)a.nb * (KSL + 8) * 2 + 127) & ~(size_t)127) +
+                       (size_t)waves * D * NR * (PK ? kPkSegBytes : 16 * 256);
     static size_t attr = 0;
     if (lds > attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_ml<MODE, NR, KSL, D>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_ml<MODE, NR, KSL, D, PK>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {  // not launched: the engine reports it with its launch errors
             launch_error_set(e, "k_gemv_ml: dynamic LDS size");
@@ -885,7 +956,7 @@ static void launch_ml(hipStream_t s, const GemvArgs& a, int blocks, int KS, floa
         }
         attr = lds;
     }
-    hipLaunchKernelGGL((k_gemv_ml<MODE, NR, KSL, D>), dim3(blocks, KS), dim3(64 * waves), lds, s, a, ws);
+    hipLaunchKernelGGL((k_gemv_ml<MODE, NR, KSL, D, PK>), dim3(blocks, KS), dim3(64 * waves), lds, s, a, ws);
 }
 
 // workgroups of 4 streaming waves: every group once, capped at `cap` workgroups (grid-stride)
@@ -931,6 +1002,14 @@ void gemv_mf_geglu(hipStream_t s, const GemvArgs& a) {  // K = 2048, gate|up row
     // (a.ssq: x = h, normalised on load from o_proj's partial sums of squares -- unstaged, norm_w read)
     // a.Wf: the fragment-major weight image (1-KiB lane-linear loads; the decode step passes it)
     const bool staged = a.norm_w && !a.ssq;
+    // a.Wp: the fragment-major 13-bit image (pgmi_set_decode_packed_batched), in the K split of the bf16 launch it
+    // replaces -- 4 x 512 staged (the row-major and the image form alike), 8 x 256 for the image's
+    // normalise-on-load form -- so the sums, and the outputs, are that launch's bit for bit
+    if (a.Wp && (staged || a.Wf)) {
+        if (staged) launch_mf<GV_GEGLU, 2, 512, 4, 1, false, false, false, true>(s, a, 256, 1, nullptr);
+        else launch_mf<GV_GEGLU, 2, 256, 8, 1, true, false, false, true>(s, a, 256, 1, nullptr);
+        return;
+    }
     if (a.Wf) {
         GemvArgs r = a;
         r.W = a.Wf;
@@ -971,6 +1050,16 @@ int gemv_mf_logits(hipStream_t s, const GemvArgs& a, int max_blocks) {  // K = 2
     // (the register-streamed form at 512 / 1,024 / 2,048 workgroups measured no faster: 1.741-1.768 ms; again in
     // round 5 with the peeled loop: B = 8 step 1.283 -> 1.330-1.341 ms, profiles/r05_b8_lm_mf_ab.txt)
     const int blocks = ms_blocks(a.n_units, max_blocks < 256 ? max_blocks : 256);
+    // a.Wp: the ring carries the 13-bit image's pieces (same depth, same k-block rotation, same MFMA order)
+    // Same box, one process, B = 8 / B = 16 step: 1.272 -> 1.291 / 1.338 -> 1.360 ms with lm_head alone packed
+    // (profiles/packed_batched_ab.txt): the rebuild sits in the ring wave's chain between a slot's arrival and its
+    // MFMAs, and costs more than 3/16 fewer bytes give back -- off by default, not in the recommended mask.  The
+    // register-streamed form was not built packed (its bf16 form: above).
+    if (a.Wp) {
+        if (a.nb > 8) launch_ml<GV_LOGITS, 1, 2048, 5, true>(s, a, blocks, 1, nullptr);
+        else launch_ml<GV_LOGITS, 1, 2048, 6, true>(s, a, blocks, 1, nullptr);
+        return blocks;
+    }
     // 9..16 rows: a 5-deep ring.  The 6-deep one and 16 staged rows are 164,096 B of dynamic LDS, past the CU's
     // 160 KiB; 5 slots make 147,712 B.  The ring's depth only changes when a k block is fetched, not the order the
     // MFMAs accumulate them in, so a row's logits are the same bits under either instance.
@@ -983,7 +1072,11 @@ int gemv_mf_logits(hipStream_t s, const GemvArgs& a, int max_blocks) {  // K = 2
 // combine: h (a.out) += down(x); hn = RMSNorm(h) with norm_w (nullptr: h only)
 void gemv_mf_res_norm(hipStream_t s, const GemvArgs& a, float* ws, const uint16_t* norm_w, float eps, uint16_t* hn) {
     const int KS = a.K / 2048;  // <= 8 (checked by the caller: gemv_res_norm)
-    if (a.Wf) {
+    if (a.Wp) {
+        // the 13-bit image in the K split of the bf16 launch it replaces (8 x 256 over the image, 4 x 512 over the rows)
+        if (a.Wf) launch_mf<GV_RES, 1, 256, 8, 1, false, false, false, true>(s, a, 32, KS, ws);
+        else launch_mf<GV_RES, 1, 512, 4, 1, false, false, false, true>(s, a, 32, KS, ws);
+    } else if (a.Wf) {
         // the fragment-major image (the decode step passes it), one-deep streams: same box, B = 8 step
         // 1.3461-1.3489 -> 1.3336-1.3339 ms against the two-deep row-major form below (the image with the
         // two-deep streams read slower: profiles/r05_b8_fragment_image_ab.txt); 32 x 8 workgroups (64 / 16 x 8:
@@ -1012,7 +1105,9 @@ void gemv_mf_res(hipStream_t s, const GemvArgs& a, float* ws) {
         // register-streamed MFMA form, 4 waves x 512 of each 2,048-wide K slice, 32 x 8 workgroups
         // (every row group of a slice once): B = 8 step 1.737 -> 1.704 ms against the LDS-DMA ring
         // (64 / 128 x 8 workgroups: 1.710 / 1.744)
-        launch_mf<GV_RES, 1, 512, 4, 2>(s, a, 32, KS, ws);
+        // (a.Wp: the 13-bit image, one-deep streams in the same 4 x 512 split)
+        if (a.Wp) launch_mf<GV_RES, 1, 512, 4, 1, false, false, false, true>(s, a, 32, KS, ws);
+        else launch_mf<GV_RES, 1, 512, 4, 2>(s, a, 32, KS, ws);
         const int nn = a.nb * a.n_units;
         hipLaunchKernelGGL(k_mf_combine, dim3((nn + 255) / 256), dim3(256), 0, s, ws, KS, a.nb, a.n_units, a.out);
         return;

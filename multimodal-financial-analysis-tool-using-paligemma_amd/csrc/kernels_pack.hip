@@ -1,4 +1,5 @@
-// kernels_pack.hip -- builds the 13-bit weight images of the batch-1/2 decode GEMVs (pack13.h): pass one finds
+// kernels_pack.hip -- builds the 13-bit weight images of the decode GEMVs (pack13.h; row-major segments for batch
+// 1-2, fragment-major ones for the batched step): pass one finds
 // a tensor's exponent range (does it fit?), pass two writes the image.  Run once per pgmi_prepare, off the hot path.
 #include "launch.h"
 #include "pack13.h"
@@ -49,6 +50,28 @@ __global__ void __launch_bounds__(256) k_pk_pack(const uint16_t* __restrict__ W,
     *reinterpret_cast<unsigned*>(dst + pk_off_h(l)) = s.h;
 }
 
+// the fragment-major gather (pack13.h): one thread per (segment, lane) of the ceil(rows / 16) x K / 128 segments; a
+// lane whose row is past the last one encodes zeros
+__global__ void __launch_bounds__(256) k_pk_pack_mf(const uint16_t* __restrict__ W, long rows, int K, long n_items,
+                                                    int e_hi, uint8_t* __restrict__ out) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_items) return;
+    const int l = (int)(t & 63);
+    const long seg = t >> 6, kbs = K / kPkMfK;
+    const long gr = seg / kbs, kb = seg % kbs;
+    const long row = pk_mf_row(gr, l);
+    uint4 f[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        f[c] = row < rows ? ldg16(W + row * K + pk_mf_k(kb, l, c)) : make_uint4(0, 0, 0, 0);
+    const PkSeg s = pk_encode(f, e_hi);
+    uint8_t* dst = out + seg * kPkSegBytes;
+    *reinterpret_cast<uint4*>(dst + pk_off_a(l)) = s.a;
+    *reinterpret_cast<uint4*>(dst + pk_off_b(l)) = s.b;
+    *reinterpret_cast<uint4*>(dst + pk_off_n(l)) = s.n;
+    *reinterpret_cast<unsigned*>(dst + pk_off_h(l)) = s.h;
+}
+
 void pk_scan(hipStream_t s, const uint16_t* W, long numel, unsigned* stat) {
     const long n16 = numel / 8;
     long blocks = (n16 + 255) / 256;
@@ -59,6 +82,11 @@ void pk_scan(hipStream_t s, const uint16_t* W, long numel, unsigned* stat) {
 void pk_pack(hipStream_t s, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out) {
     const long n = rows * (K / kPkSegK) * 64;
     hipLaunchKernelGGL(k_pk_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, n, e_hi, out);
+}
+
+void pk_pack_mf(hipStream_t s, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out) {
+    const long n = (long)pk_mf_groups(rows) * (K / kPkMfK) * 64;
+    hipLaunchKernelGGL(k_pk_pack_mf, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, rows, K, n, e_hi, out);
 }
 
 }  // namespace pgmi

@@ -118,6 +118,7 @@ void gemv_qkv(hipStream_t s, int B, int nh, int nkv, const uint16_t* h, const ui
               int st_stride = 0);
 // The 13-bit image of a weight matrix (pack13.h) for the streaming GEMVs at B <= 2 (gate|up, down at K = 16384,
 // lm_head): img null = read the bf16 rows; base2 = pk_base2(e_hi).  Same outputs, bit for bit, either way.
+// At B >= gemv_mf_min_batch() the same arguments take the fragment-major image (pk_pack_mf) for the MFMA forms.
 struct PkW {
     const uint8_t* img = nullptr;
     unsigned base2 = 0;
@@ -126,6 +127,8 @@ struct PkW {
 // one >= 1 (caller presets 0 / 0xFFFFFFFF); out: pk_image_bytes(rows, K) bytes, K a multiple of 2048
 void pk_scan(hipStream_t s, const uint16_t* W, long numel, unsigned* stat);
 void pk_pack(hipStream_t s, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out);
+// the fragment-major image the batched (B >= 3) MFMA GEMVs read (pack13.h): pk_image_bytes_mf(rows, K) bytes
+void pk_pack_mf(hipStream_t s, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out);
 // LoRA (kernels_lora.hip, the rule of lora.h): out[N][K] = bf16(W + (B . A) * scaling) from the pristine W (bf16),
 // A[r][K] and B[N][r] in fp32 (all 16-B aligned, K a multiple of 8, r in [1, 256]); out does not overlap W.  lora_widen:
 // n factor values of dtype PGMI_DTYPE_* on the device to fp32.
@@ -138,7 +141,8 @@ void gemv_res(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W,
 // gemv_res, then hn = RMSNorm(h) with norm_w (nullptr: none); on the batched MFMA path the norm is
 // fused into the K-split combine (one workgroup per row)
 void gemv_res_norm(hipStream_t s, int B, int K, const uint16_t* x, const uint16_t* W, int N, uint16_t* h_inout,
-                   float* ws, const uint16_t* norm_w, float eps, uint16_t* hn, const uint16_t* Wf = nullptr);
+                   float* ws, const uint16_t* norm_w, float eps, uint16_t* hn, const uint16_t* Wf = nullptr,
+                   PkW pk = {});
 // the fragment-major image of a [rows][K] matrix for the batched decode GEMVs (rows % 16 == 0, K % 32 == 0)
 // (qkv: in the batched q|k|v GEMV's row order)
 void mf_swizzle(hipStream_t s, const uint16_t* W, int rows, int K, uint16_t* out, bool qkv = false);

@@ -21,6 +21,13 @@
 //   bytes [3072, 3328):  4 B per lane, bit 4 of u: weight (c, 2p) at bit 4c + p, (c, 2p + 1) at bit 16 + 4c + p
 // so every wave load reads one contiguous, 128-byte-aligned run.  A pair of weights (2p, 2p + 1) -- one dword of
 // the bf16 fragment -- comes out of each plane with one shift, both halves at once.
+//
+// The fragment-major image (batched decode, B >= 3: kernels_gemv_mfma.hip, the PK forms).  The same record and
+// the same four pieces, another gather: a segment is one 16-row group x 128-k block of a [rows][K] matrix, and lane
+// l = (n = l & 15, g = l >> 4), chunk c < 4, element j < 8 holds row 16 gr + n at k = 128 kb + 32 c + 8 g + j -- the
+// four B fragments k_gemv_mf's issue loads for k block kb.  Segments follow the fragment-major bf16 image: segment
+// gr * (K / 128) + kb over the ceil(rows / 16) groups (gate|up as one 2 I x H matrix: the up rows' groups after the
+// gate rows').  Rows past the last one are encoded as zeros (exponent field 0, u = 0); their results are never stored.
 #include "common.h"
 
 namespace pgmi {
@@ -108,5 +115,16 @@ PK_HD int pk_off_n(int l) { return 2048 + 16 * l; }
 PK_HD int pk_off_h(int l) { return 3072 + 4 * l; }
 
 inline int64_t pk_image_bytes(int64_t rows, int64_t K) { return rows * (K / kPkSegK) * kPkSegBytes; }
+
+// ---- the fragment-major gather (16-row group x 128-k block per segment)
+constexpr int kPkMfRows = 16, kPkMfK = 128;
+
+PK_HD int64_t pk_mf_groups(int64_t rows) { return (rows + kPkMfRows - 1) / kPkMfRows; }
+PK_HD int64_t pk_mf_seg(int64_t gr, int64_t kb, int64_t K) { return gr * (K / kPkMfK) + kb; }
+// the weight at (lane l, chunk c, element 0) of segment (gr, kb): its row (may be past the last: a zero) and k
+PK_HD int64_t pk_mf_row(int64_t gr, int l) { return kPkMfRows * gr + (l & 15); }
+PK_HD int64_t pk_mf_k(int64_t kb, int l, int c) { return kPkMfK * kb + 32 * c + 8 * (l >> 4); }
+
+inline int64_t pk_image_bytes_mf(int64_t rows, int64_t K) { return pk_mf_groups(rows) * (K / kPkMfK) * kPkSegBytes; }
 
 }  // namespace pgmi

@@ -87,6 +87,12 @@ SIGNATURES = {
     "pgmi_pack13_bytes": (i64, [i64, i64]),
     "pgmi_pack13_encode": (i32, [vp, i64, i64, i32, vp]),
     "pgmi_pack13_decode": (i32, [vp, i64, i64, i32, vp]),
+    "pgmi_set_decode_packed_batched": (i32, [vp, i32]),
+    "pgmi_decode_packed_batched_info": (i32, [vp, ctypes.POINTER(i64), i32]),
+    "pgmi_decode_packed_batched_tensor": (i32, [vp, i32, i32]),
+    "pgmi_pack13_bytes_mf": (i64, [i64, i64]),
+    "pgmi_pack13_encode_mf": (i32, [vp, i64, i64, i32, vp]),
+    "pgmi_pack13_decode_mf": (i32, [vp, i64, i64, i32, vp]),
     "pgmi_lora_create": (i32, [vp, ctypes.POINTER(i32)]),
     "pgmi_lora_add": (i32, [vp, i32, ctypes.c_char_p, vp, i32, ctypes.POINTER(i64), vp, i32, ctypes.POINTER(i64), f32,
                             i32, vp]),

@@ -628,6 +628,28 @@ class Engine:
             N.check(rc, "pgmi_decode_packed_tensor")
         return rc == 1
 
+    def set_decode_packed_batched(self, mask: int) -> None:
+        """Batched decode (3..16 rows) on the fragment-major 13-bit weight images: 0 off (the default), or a mask of
+        kinds (1 gate|up, 2 down, 4 lm_head; 7 all).  Results are bit-identical either way
+        (pgmi_set_decode_packed_batched)."""
+        N.check(self.lib.pgmi_set_decode_packed_batched(self.ctx, int(mask)), "pgmi_set_decode_packed_batched")
+
+    def decode_packed_batched_info(self) -> dict:
+        """How the batched decode step reads its 2 x layers + 1 streamed tensors now
+        (pgmi_decode_packed_batched_info)."""
+        v = (ctypes.c_int64 * 6)()
+        N.check(self.lib.pgmi_decode_packed_batched_info(self.ctx, v, 6), "pgmi_decode_packed_batched_info")
+        return {"mask": v[0], "scanned": v[1], "packed": v[2], "raw": v[3], "packed_bytes": v[4],
+                "alloc_failed": bool(v[5])}
+
+    def decode_packed_batched_tensor(self, kind: int, layer: int = 0) -> bool:
+        """Is the tensor of kind 1 gate|up / 2 down (of `layer`) / 4 lm_head read from its fragment-major 13-bit
+        image by the batched step now?"""
+        rc = self.lib.pgmi_decode_packed_batched_tensor(self.ctx, int(kind), int(layer))
+        if rc < 0:
+            N.check(rc, "pgmi_decode_packed_batched_tensor")
+        return rc == 1
+
     def decode_kernel(self, which: int, layer: int, B: int) -> None:
         """One decode projection on the decode workspace (pgmi_decode_kernel): 1 o_proj, 2 gate|up, 3 down, 4 lm_head."""
         self._ready()
