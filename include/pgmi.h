@@ -161,6 +161,23 @@ int pgmi_decode_steps(pgmi_ctx* ctx, int64_t* ids, int B, void* kv, int kv_batch
 int pgmi_lm_forward_ragged(pgmi_ctx* ctx, const int64_t* ids, const void* image_feats, int n_img_rows,
                            const void* embeds, int B, int L, const int64_t* positions, const int32_t* lens, void* kv,
                            int kv_batch, int kv_max, int kv_start, float* logits, int logits_rows, void* stream);
+/* ---- prefix-LM prefill: a prompt attended from everywhere, the tokens after it causally --------
+ * pgmi_lm_forward and _ragged are non-causal over the new tokens (the reference's zero mask), which is right for
+ * a prompt and wrong for a teacher-forced answer: the row that predicts answer token j + 1 would have attended it.
+ * Here row b has a prefix of prefix_lens[b] tokens (HOST int32 [B], 0 <= prefix_lens[b] <= lens[b], or <= L when
+ * lens is NULL: the lock-step call).  Token j attends keys [0, kv_start + max(prefix_lens[b], j + 1)) of its own
+ * row, never past kv_start + lens[b]: the kv_start cached rows and the prefix from every token, the tokens after
+ * the prefix causally.  prefix_lens[b] = 0 is fully causal over the new tokens; prefix_lens[b] = lens[b] for every
+ * row launches exactly what pgmi_lm_forward / _ragged launch (bit-identical logits and K/V rows).  Positions are
+ * the caller's (to continue with decode steps as the reference counts them, token j >= prefix_lens[b] has position
+ * j + 1: the first decode position after an L-token prefill is L + 1).  Embeds are not taken.  logits_rows as
+ * pgmi_lm_forward (lens NULL) or _ragged: a row's last token attends all its keys either way.
+ * EAGER ONLY: the call runs its launches on the caller's stream; it neither replays, captures nor records a key in
+ * the prefill graph cache (pgmi_graph_count is unchanged by it), whatever pgmi_set_prefill_graph says.
+ * PGMI_E_ARG: a prefix length outside [0, lens[b]], and everything pgmi_lm_forward(_ragged) refuses. */
+int pgmi_lm_forward_prefix(pgmi_ctx* ctx, const int64_t* ids, const void* image_feats, int n_img_rows, int B, int L,
+                           const int64_t* positions, const int32_t* lens, const int32_t* prefix_lens, void* kv,
+                           int kv_batch, int kv_max, int kv_start, float* logits, int logits_rows, void* stream);
 /* n_steps >= 1 decode steps (inference.py:55-78 loop body) for B rows of different lengths: kv_lens
  * and positions are HOST int32 [B].  At step t row b writes K/V at row kv_lens[b] + t, attends keys
  * [0, kv_lens[b] + t] and uses rotary position positions[b] + t (after a ragged prefill
@@ -602,6 +619,18 @@ int pgmi_op_attention_ex(pgmi_ctx* ctx, const void* q, const void* k, const void
                          int H, int Hkv, int head_dim, int kv_layout, float scale, int scale_div, const void* mask,
                          int mask_dtype, int64_t m_b_stride, int64_t m_h_stride, int64_t m_q_stride, void* probs,
                          void* stream);
+/* The prefill attention of pgmi_lm_forward_prefix on raw bf16 buffers, through the launcher the prefill uses (not
+ * the reference-order kernel of pgmi_op_attention_ex): q/o (B, Lq, H, hd), k/v rows of Lk keys per batch row in
+ * kv_layout 0 (B, Lk, Hkv, hd) or 1 (B, Hkv, Lk, hd), hd = 256, B <= 16.  Query j of row b attends keys
+ * [0, min(klen[b], kv_start + max(prefix_lens[b], j + 1))); klen (HOST int32 [B], kv_start < klen[b] <= kv_start +
+ * Lq <= Lk; NULL: kv_start + Lq for every row) and prefix_lens (HOST int32 [B], 0 <= prefix_lens[b] <= klen[b] -
+ * kv_start).  Keys at or past a row's klen[b] are never read.  s = bf16(bf16(q.k) * scale). */
+int pgmi_op_attention_prefix(pgmi_ctx* ctx, const void* q, const void* k, const void* v, void* o, int B, int Lq,
+                             int Lk, int H, int Hkv, int head_dim, int kv_layout, float scale, int kv_start,
+                             const int32_t* klen, const int32_t* prefix_lens, void* stream);
+/* The key ranges (>= 1) the kernel of pgmi_op_attention_prefix splits the kv_start + Lq keys of such a call into on
+ * this context (more than one: partials in the context's scratch, merged by a second kernel); negative: an error. */
+int pgmi_op_attention_prefix_splits(pgmi_ctx* ctx, int B, int Lq, int H, int Hkv, int kv_start);
 /* apply_rotary_pos_emb for one projection (modeling_gemma.py:187-199) with the caller's cos/sin rows
  * (GemmaRotaryEmbedding.forward's output, :155-185): x (rows, heads*hd) -> out = bf16(bf16(x*cos) +
  * bf16(rotate_half(x)*sin)), cos/sin bf16 (rows, hd). */

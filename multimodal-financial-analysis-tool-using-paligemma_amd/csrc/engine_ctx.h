@@ -187,7 +187,8 @@ struct pgmi_ctx {
     StepState* step;
     StepState* pstep;  // the generate-loop prefill's last-row attention (flash-decoding over the prompt's keys)
     StepState* rstep;  // the ragged step's records, one per batch row ([max_batch], pgmi_decode_ragged)
-    int* d_rlens;      // ragged prefill: [0, 16) each row's token count, [16, 32) its attended key count
+    int* d_rlens;      // ragged prefill: [0, 16) each row's token count, [16, 32) its attended key count;
+                       // prefix prefill: [16, 32) as well (lock-step rows: kv_start + L), [32, 48) its prefix length
     int64_t* d_ids;
     uint16_t* d_emb;             // staged input rows of pgmi_decode_embeds ([max_batch][hidden] bf16)
     float* d_mask;               // staged additive decode mask ([max_batch][max_kv] fp32, pgmi_decode_embeds_dev)
@@ -271,6 +272,7 @@ struct PrefillRun {
     float* logits;           // the batch's logits (lm_logits takes the group's slice)
     int logits_rows;
     bool ragged;
+    bool prefix = false;     // a prefix-LM call with at least one row whose prefix is shorter than the row
 };
 
 // One decode step's launches, shared by decode_body and the stage hook (pgmi_debug_decode_stage): what the
@@ -311,6 +313,10 @@ bool run_last_only(const pgmi_ctx* x, const PrefillRun& r);
 void lm_in_norm(const pgmi_ctx* x, const PrefillRun& r);
 void lm_qkv(const pgmi_ctx* x, const PrefillRun& r, int i);
 void lm_attn(const pgmi_ctx* x, const PrefillRun& r, int i);
+// the prefix form's row values to the device (d_rlens segments 2 and 3), outside any graph
+void set_prefix_rows(const pgmi_ctx* x, hipStream_t s, const RowInts& klen, const RowInts& pfx, int B);
+// the attention launcher of lm_attn: a with the group's key counts (ragged or causal) and prefix lengths (causal)
+void lm_attn_launch(const pgmi_ctx* x, hipStream_t s, AttnArgs a, int b0, int kv_start, bool ragged, bool causal);
 void lm_o_proj(const pgmi_ctx* x, const PrefillRun& r, int i);
 void lm_gate_up(const pgmi_ctx* x, const PrefillRun& r, int i);
 void lm_down(const pgmi_ctx* x, const PrefillRun& r, int i);

@@ -402,6 +402,56 @@ int pgmi_op_attention(pgmi_ctx* x, const void* q, const void* k, const void* v, 
     return 0;
 }
 
+int pgmi_op_attention_prefix(pgmi_ctx* x, const void* q, const void* k, const void* v, void* o, int B, int Lq, int Lk,
+                             int H, int Hkv, int hd, int kv_layout, float scale, int kv_start, const int32_t* klen,
+                             const int32_t* prefix_lens, void* stream) {
+    int rc;
+    if (!x || !q || !k || !v || !o || !prefix_lens) return fail(PGMI_E_ARG, "null argument");
+    if ((rc = ensure_prepared(x))) return rc;
+    if (hd != 256) return fail(PGMI_E_ARG, "head_dim must be 256");
+    if (B < 1 || B > kMaxRows || Lq < 1 || Hkv < 1 || H < 1 || H % Hkv != 0 || H / Hkv > 16)
+        return fail(PGMI_E_ARG, "bad shape");
+    if (kv_layout != 0 && kv_layout != 1) return fail(PGMI_E_ARG, "kv_layout must be 0 (B,L,Hkv,hd) or 1 (B,Hkv,L,hd)");
+    if (kv_start < 0 || Lk < 1 || kv_start + Lq > Lk) return fail(PGMI_E_ARG, "kv_start + Lq keys exceed Lk");
+    RowInts rk{}, rp{};
+    bool causal = false;
+    for (int b = 0; b < B; ++b) {
+        const int kl = klen ? klen[b] : kv_start + Lq;
+        if (kl <= kv_start || kl > kv_start + Lq) return fail(PGMI_E_ARG, "klen[b] must be in (kv_start, kv_start + Lq]");
+        if (prefix_lens[b] < 0 || prefix_lens[b] > kl - kv_start)
+            return fail(PGMI_E_ARG, "prefix_lens[b] must be in [0, klen[b] - kv_start]");
+        rk.v[b] = kl;
+        rp.v[b] = prefix_lens[b];
+        causal = causal || prefix_lens[b] < kl - kv_start;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    set_prefix_rows(x, s, rk, rp, B);
+    AttnArgs a{};
+    a.q = reinterpret_cast<const uint16_t*>(q); a.q_b_stride = (long)Lq * H * hd; a.q_row_stride = H * hd; a.q_head_stride = hd;
+    a.k = reinterpret_cast<const uint16_t*>(k); a.k_b_stride = (long)Lk * Hkv * hd;
+    a.k_row_stride = kv_layout == 0 ? Hkv * hd : hd; a.k_head_stride = kv_layout == 0 ? hd : Lk * hd;
+    a.v = reinterpret_cast<const uint16_t*>(v); a.v_b_stride = a.k_b_stride;
+    a.v_row_stride = a.k_row_stride; a.v_head_stride = a.k_head_stride;
+    a.o = reinterpret_cast<uint16_t*>(o); a.o_b_stride = a.q_b_stride; a.o_row_stride = H * hd; a.o_head_stride = hd;
+    a.Lq = Lq; a.Lk = kv_start + Lq; a.G = H / Hkv; a.n_kv = Hkv; a.B = B; a.scale = scale;
+    a.ws = x->ws; a.ws_floats = (long)(x->ws_bytes / sizeof(float));
+    lm_attn_launch(x, s, a, 0, kv_start, klen != nullptr, causal);
+    LAUNCHCHK();
+    return 0;
+}
+
+int pgmi_op_attention_prefix_splits(pgmi_ctx* x, int B, int Lq, int H, int Hkv, int kv_start) {
+    int rc;
+    if (!x) return fail(PGMI_E_ARG, "null argument");
+    if ((rc = ensure_prepared(x))) return rc;
+    if (B < 1 || B > kMaxRows || Lq < 1 || Hkv < 1 || H < 1 || H % Hkv != 0 || kv_start < 0)
+        return fail(PGMI_E_ARG, "bad shape");
+    AttnArgs a{};
+    a.Lq = Lq; a.Lk = kv_start + Lq; a.G = H / Hkv; a.n_kv = Hkv; a.B = B;
+    a.ws = x->ws; a.ws_floats = (long)(x->ws_bytes / sizeof(float));
+    return attention_prefill_splits(a);
+}
+
 int pgmi_op_attention_ex(pgmi_ctx* x, const void* q, const void* k, const void* v, void* o, int B, int Lq, int Lk,
                          int H, int Hkv, int hd, int kv_layout, float scale, int scale_div, const void* mask,
                          int mask_dtype, int64_t m_b_stride, int64_t m_h_stride, int64_t m_q_stride, void* probs,

@@ -39,8 +39,11 @@
 // 4. What each call rewrites outside the graph, before it: the positions (dpos, lm_begin), a ragged prefill's row
 //    lengths (d_rlens, lm_begin), the step records (step / rstep: set when the call does not continue the last
 //    one, advanced by the step's last kernel inside the graph), and the staged inputs of a graphed decode step
-//    (d_ids, d_emb, d_mask).  The host mirrors (tn_rows, step_known and its fellows) are written around the body,
-//    never in it.
+//    (d_ids, d_emb, d_mask).  A prefix-LM prefill (pgmi_lm_forward_prefix) rewrites its rows' key counts and prefix
+//    lengths (d_rlens segments 2 and 3) the same way, and then has no graph at all: it runs its body on the caller's
+//    stream, and neither looks up nor inserts a key in pgraphs (the per-query key limits of k_attn_fs are not a
+//    replayed form; a scoring call's buffers are fresh each time).  The host mirrors (tn_rows, step_known and its
+//    fellows) are written around the body, never in it.
 //
 // 5. Non-kernel nodes: a prefill graph holds three kinds, per row group -- the memset of pstep->kv_len and the 2-D
 //    copy into lastrows of lm_last_row_tail (logits_rows 2), or the 2-D copy into lastrows of lm_logits

@@ -124,13 +124,34 @@ static AttnArgs lm_attn_args(const pgmi_ctx* x, const PrefillRun& r, int i) {
     a.Lq = r.L; a.Lk = r.kv_start + r.L; a.G = NH / NKV; a.n_kv = NKV; a.B = r.B;
     a.scale = 1.0f / std::sqrt((float)HD);  // / math.sqrt(head_dim) (:266): exact power of two
     a.ws = x->ws; a.ws_floats = (long)(x->ws_bytes / sizeof(float));
-    // ragged: row b's real tokens attend its own real keys only
-    a.klen = r.ragged ? x->d_rlens + kMaxRows + r.b0 : nullptr;
-    return a;
+    return a;  // klen: lm_attn_launch (the last-row tail is lock-step)
+}
+
+void set_prefix_rows(const pgmi_ctx* x, hipStream_t s, const RowInts& klen, const RowInts& pfx, int B) {
+    set_row_ints(s, x->d_rlens + kMaxRows, klen, pfx, B);
+}
+
+// The one launcher of the prefill attention with per-row values (lm_attn and pgmi_op_attention_prefix): causal --
+// some row of the call has tokens after its prefix -- takes the per-query key limits of k_attn_fs over the rows'
+// key counts and prefix lengths (set_prefix_rows); otherwise a call is what it was, the ragged form over the key
+// counts (a ragged row's real tokens attend its own real keys only) or the lock-step kernels.
+void lm_attn_launch(const pgmi_ctx* x, hipStream_t s, AttnArgs a, int b0, int kv_start, bool ragged, bool causal) {
+    a.klen = ragged || causal ? x->d_rlens + kMaxRows + b0 : nullptr;
+    if (!causal) {
+        attention_prefill(s, 256, a);
+        return;
+    }
+    AttnPrefixArgs p{};
+    static_cast<AttnArgs&>(p) = a;
+    p.pfx = x->d_rlens + 2 * kMaxRows + b0;
+    p.kv_start = kv_start;
+    attention_prefill_prefix(s, p);
 }
 
 // layer i's attention: Qr, the cache rows -> AO
-void lm_attn(const pgmi_ctx* x, const PrefillRun& r, int i) { attention_prefill(r.s, 256, lm_attn_args(x, r, i)); }
+void lm_attn(const pgmi_ctx* x, const PrefillRun& r, int i) {
+    lm_attn_launch(x, r.s, lm_attn_args(x, r, i), r.b0, r.kv_start, r.ragged, r.prefix);
+}
 
 // layer i's o_proj partial slabs, then their sum + residual and the post-attention norm: AO, Hs -> Hs, Tn
 void lm_o_proj(const pgmi_ctx* x, const PrefillRun& r, int i) {
@@ -383,7 +404,7 @@ int pgmi_embed(pgmi_ctx* x, const int64_t* ids, int rows, void* out, void* strea
 
 static int lm_body(const pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
                    const void* embeds, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
-                   int logits_rows, bool ragged);
+                   int logits_rows, bool ragged, bool prefix = false);
 
 static int lm_rows(const pgmi_ctx* x, const PrefillRun& r);
 
@@ -427,16 +448,50 @@ static int lm_forward(pgmi_ctx* x, const int64_t* ids, const void* image_feats, 
     return 0;
 }
 
+int pgmi_lm_forward_prefix(pgmi_ctx* x, const int64_t* ids, const void* image_feats, int n_img_rows, int B, int L,
+                           const int64_t* positions, const int32_t* lens, const int32_t* prefix_lens, void* kv,
+                           int kv_batch, int kv_max, int kv_start, float* logits, int logits_rows, void* stream) {
+    if (!prefix_lens || !ids) return fail(PGMI_E_ARG, "null argument");
+    const bool ragged = lens != nullptr;
+    // before lm_begin writes anything: a refused call leaves the last call's positions, lengths and final rows
+    for (int b = 0; b < B && b < kMaxRows; ++b)
+        if (prefix_lens[b] < 0 || prefix_lens[b] > (ragged ? lens[b] : L))
+            return fail(PGMI_E_ARG, "prefix_lens[b] must be in [0, lens[b]]");
+    int rc;
+    if ((rc = lm_begin(x, ids, nullptr, B, L, positions, lens, ragged, kv, kv_batch, kv_max, kv_start, logits,
+                       &logits_rows, stream)))
+        return rc;
+    // the rows' key counts and prefix lengths -> the device, outside any graph (there is none here); causal: some
+    // row has tokens after its prefix -- otherwise every launch is pgmi_lm_forward's / _ragged's
+    RowInts rk{}, rp{};
+    bool causal = false;
+    for (int b = 0; b < B; ++b) {
+        const int len = ragged ? lens[b] : L;
+        rk.v[b] = kv_start + len;
+        rp.v[b] = prefix_lens[b];
+        causal = causal || prefix_lens[b] < len;
+    }
+    set_prefix_rows(x, (hipStream_t)stream, rk, rp, B);
+    LAUNCHCHK();
+    // eager, on the caller's stream: no key is looked up or inserted (engine_graph.h, point 4)
+    if ((rc = lm_body(x, (hipStream_t)stream, ids, image_feats, n_img_rows, nullptr, B, L, kv, kv_batch, kv_max,
+                      kv_start, logits, logits_rows, ragged, causal)))
+        return rc;
+    x->tn_rows = logits_rows == 2 && L > 1 ? 0 : (long)B * L;
+    LAUNCHCHK();
+    return 0;
+}
+
 static int lm_body(const pgmi_ctx* x, hipStream_t s, const int64_t* ids, const void* image_feats, int n_img_rows,
                    const void* embeds, int B, int L, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,
-                   int logits_rows, bool ragged) {
+                   int logits_rows, bool ragged, bool prefix) {
     lm_entry(x, s, ids, image_feats, n_img_rows, embeds, B, L, ragged);
     // the layers: row groups of at most kPrefillGroup sequences, one after the other (the merge above ran for the
     // whole batch: the k-th <image> token of the batch takes image row k); a group's rows of Hs / Tn, its positions,
     // lengths, KV rows and logits are its slice of the batch's, everything else is scratch that the groups share
     for (int b0 = 0; b0 < B; b0 += kPrefillGroup) {
         const PrefillRun r{s, b0, std::min(kPrefillGroup, B - b0), L, kv, kv_batch, kv_max, kv_start, logits,
-                           logits_rows, ragged};
+                           logits_rows, ragged, prefix};
         if (int rc = lm_rows(x, r)) return rc;
     }
     return 0;

@@ -506,7 +506,7 @@ int pgmi_prepare(pgmi_ctx* x) {
         if ((rc = dalloc_t(x, &x->step, 1))) return rc;
         if ((rc = dalloc_t(x, &x->pstep, 1))) return rc;
         if ((rc = dalloc_t(x, &x->rstep, kMaxRows))) return rc;
-        if ((rc = dalloc_t(x, &x->d_rlens, 2 * kMaxRows))) return rc;
+        if ((rc = dalloc_t(x, &x->d_rlens, 3 * kMaxRows))) return rc;
         if ((rc = dalloc_t(x, &x->amax_v, (size_t)argmax_scratch_parts()))) return rc;
         if ((rc = dalloc_t(x, &x->amax_i, (size_t)argmax_scratch_parts()))) return rc;
         if ((rc = dalloc_t(x, &x->d_ids, (size_t)B))) return rc;

@@ -21,6 +21,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace pgmi {
 
@@ -839,8 +840,19 @@ __device__ __forceinline__ void fs_vm_wait(int n) {  // s_waitcnt vmcnt(G * min(
 // neither scored (masked to -inf) nor loaded (the row index is clamped); a key range that holds none of the
 // row's keys does no tile at all and leaves (m = -1e30, l = 0, O = 0), weight exp(-1e30 - M) = 0 in the
 // combine.  KL = false: a.Lk keys for every row (the kernels as they were)
-template <int HD, int NW, int LW, int ST, bool P2, bool KL = false>
-__global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int ns, int tps) {
+// CA (with KL): prefix-LM prefill -- query position j of batch row b attends keys [0, lim) with
+// lim = min(klen[b], kv_start + max(pfx[b], j + 1)): the cached rows and the row's prefix from every position,
+// the tokens after the prefix causally.  1 <= lim <= klen[b].  A workgroup walks the tiles below its bound, the
+// largest lim of its query rows (block-uniform, and one expression for the loader and the compute waves, which
+// meet at barriers counted by it); the tiles and keys past it are neither loaded nor scored.  finish masks
+// key >= lim of the lane's own row; a row with no key in a tile (or in a whole key range) keeps m at its finite
+// start with e = 0 and l unchanged, and the range's partial (m = -1e30, l = 0, O = 0) has weight 0 in the combine
+template <bool CA>
+using FsArgs = std::conditional_t<CA, AttnPrefixArgs, AttnArgs>;
+
+template <int HD, int NW, int LW, int ST, bool P2, bool KL = false, bool CA = false>
+__global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(FsArgs<CA> a, int ns, int tps) {
+    static_assert(!CA || KL, "the prefix form reads the rows' key counts");
     using I = FSInfo<HD>;
     constexpr int KS = I::KS, CT = I::CT, CH = I::CH, CR = I::CR, ROWB = I::ROWB, TILEB = I::TILEB;
     constexpr int SLOTB = I::SLOTB, PCS = I::PCS, GPW = PCS / LW;
@@ -855,6 +867,19 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int n
     if constexpr (KL) {
         const int kl = a.klen[b];
         Lk = kl < 1 ? 1 : (kl < a.Lk ? kl : a.Lk);
+    }
+    // CA: the row's key count (the bound of a lane's limit), then Lk becomes the workgroup's bound
+    [[maybe_unused]] const int Lrow = Lk;
+    [[maybe_unused]] int pfx = 0, kv0 = 0;
+    if constexpr (CA) {
+        pfx = a.pfx[b];
+        kv0 = a.kv_start;
+        const int nr = a.Lq * a.G;
+        int rl = (int)blockIdx.x * QB + QB - 1;  // the workgroup's last query row
+        rl = rl < nr ? rl : nr - 1;
+        const int jl = rl / a.G + 1;
+        const int lb = kv0 + (pfx > jl ? pfx : jl);
+        Lk = lb < Lrow ? lb : Lrow;
     }
     const int nt = (Lk + 31) / 32;
     const int t0 = sp * tps;
@@ -914,10 +939,19 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int n
     const int nrows = a.Lq * a.G;
     const int rbase = blockIdx.x * QB + wave * 16;
     short8 qf[KS];
+    // CA: the key limit of this lane's query row li, and the smallest limit in the wave (its first row's)
+    [[maybe_unused]] int lim = Lk, lim0 = Lk;
     {
         int qi = rbase + li;
         qi = qi < nrows ? qi : nrows - 1;  // rows past the end: a valid row, never stored
         const int qpos = qi / a.G, qhead = kvh * a.G + qi % a.G;
+        if constexpr (CA) {
+            const int q0 = (rbase < nrows ? rbase : nrows - 1) / a.G;
+            const int l1 = kv0 + (pfx > qpos + 1 ? pfx : qpos + 1);
+            const int l0 = kv0 + (pfx > q0 + 1 ? pfx : q0 + 1);
+            lim = l1 < Lrow ? l1 : Lrow;
+            lim0 = l0 < Lrow ? l0 : Lrow;
+        }
         const uint16_t* qrow = a.q + b * a.q_b_stride + (long)qpos * a.q_row_stride + qhead * a.q_head_stride;
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) qf[kk] = load_frag<HD>(qrow, true, kk, lane);
@@ -947,8 +981,8 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int n
                 ac[kt][kk & 1] = mfma16(kf, qf[kk], ac[kt][kk & 1]);
             }
     };
-    // s = bf16(bf16(k.q) * scale), keys past Lk masked (the last tile only: wave-uniform branch);
-    // returns the tile's max of row li
+    // s = bf16(bf16(k.q) * scale), keys past Lk masked (the last tile only: wave-uniform branch; CA: keys past
+    // the row's own limit, in every tile that reaches past the wave's smallest); returns the tile's max of row li
     auto finish = [&](int t, const f32x4 (&ac)[2][2], float (&sv)[2][4]) -> float {
         float mx = -INFINITY;
 #pragma unroll
@@ -958,12 +992,12 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(AttnArgs a, int n
                 const float x = rbf(ac[kt][0][j] + ac[kt][1][j]);
                 sv[kt][j] = P2 ? x * a.scale : rbf(x * a.scale);
             }
-        if (t * 32 + 32 > Lk) {
+        if (t * 32 + 32 > (CA ? lim0 : Lk)) {
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (t * 32 + kt * 16 + 4 * g + j >= Lk) sv[kt][j] = -INFINITY;
+                    if (t * 32 + kt * 16 + 4 * g + j >= (CA ? lim : Lk)) sv[kt][j] = -INFINITY;
         }
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
@@ -1118,33 +1152,43 @@ static int fs_splits(const AttnArgs& a, int HD, int QB, int want) {
     return ns < 1 ? 1 : ns;
 }
 
-template <int HD, int NW, int LW, int ST, bool P2, bool KL = false>
-static void launch_fs_t(hipStream_t s, const AttnArgs& a, int ns, int tps, dim3 grid) {
+template <int HD, int NW, int LW, int ST, bool P2, bool KL = false, bool CA = false>
+static void launch_fs_t(hipStream_t s, const FsArgs<CA>& a, int ns, int tps, dim3 grid) {
     constexpr size_t lds = (size_t)ST * FSInfo<HD>::SLOTB;
     static_assert(lds <= 160 * 1024, "LDS");
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fs<HD, NW, LW, ST, P2, KL>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fs<HD, NW, LW, ST, P2, KL, CA>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = true;
     }
-    hipLaunchKernelGGL((k_attn_fs<HD, NW, LW, ST, P2, KL>), grid, dim3(64 * (NW + LW)), lds, s, a, ns, tps);
+    hipLaunchKernelGGL((k_attn_fs<HD, NW, LW, ST, P2, KL, CA>), grid, dim3(64 * (NW + LW)), lds, s, a, ns, tps);
 }
 
-template <int HD, int NWQ = 0>
-static void launch_fs(hipStream_t s, const AttnArgs& a, int want_ns) {
+// the key ranges and the tiles per range of a launch: no empty range
+static int fs_plan(const AttnArgs& a, int HD, int QB, int want, int* tps) {
+    const int nt = (a.Lk + 31) / 32;
+    const int ns = fs_splits(a, HD, QB, want);
+    *tps = (nt + ns - 1) / ns;
+    return (nt + *tps - 1) / *tps;
+}
+
+template <int HD, int NWQ = 0, bool CA = false>
+static void launch_fs(hipStream_t s, const FsArgs<CA>& a, int want_ns) {
     // head dim 256: 4 compute waves (their registers fit 2 waves per SIMD with the loaders, not 3) and a
     // 5-slot ring (160 KiB); head dim 72: 8 compute waves, 8 slots.  NWQ > 0: that many compute waves (fewer
     // query rows per workgroup, more workgroups over the same keys: probe variants 81 / 82)
     constexpr int NW = NWQ > 0 ? NWQ : HD == 256 ? 4 : 8, LW = 4, ST = HD == 256 ? 5 : 8;
-    const int nrows = a.Lq * a.G, nt = (a.Lk + 31) / 32;
-    int ns = fs_splits(a, HD, NW * 16, want_ns);
-    const int tps = (nt + ns - 1) / ns;
-    ns = (nt + tps - 1) / tps;  // no empty range
+    const int nrows = a.Lq * a.G;
+    int tps = 0;
+    const int ns = fs_plan(a, HD, NW * 16, want_ns, &tps);
     dim3 grid((nrows + NW * 16 - 1) / (NW * 16), a.n_kv * ns, a.B);
     int e2 = 0;
     const bool p2 = std::frexp(a.scale, &e2) == 0.5f;
-    if (a.klen) {  // ragged prefill (head dim 256, the default compute-wave count): per-row key counts
+    if constexpr (CA) {  // prefix-LM prefill: per-query key limits over the rows' key counts
+        if (p2) launch_fs_t<HD, NW, LW, ST, true, true, true>(s, a, ns, tps, grid);
+        else launch_fs_t<HD, NW, LW, ST, false, true, true>(s, a, ns, tps, grid);
+    } else if (a.klen) {  // ragged prefill (head dim 256, the default compute-wave count): per-row key counts
         if constexpr (HD == 256 && NWQ == 0) {
             if (p2) launch_fs_t<HD, NW, LW, ST, true, true>(s, a, ns, tps, grid);
             else launch_fs_t<HD, NW, LW, ST, false, true>(s, a, ns, tps, grid);
@@ -1203,6 +1247,13 @@ static size_t attn_full_lds(int head_dim, int Lk) {
     const int LkP = (Lk + 31) & ~31;
     const int hdp = (head_dim + 15) / 16 * 16;
     return (size_t)16 * LkP * 4 + (size_t)16 * LkP * 2 + (size_t)2 * 32 * (hdp + 16) * 2;
+}
+
+void attention_prefill_prefix(hipStream_t s, const AttnPrefixArgs& a) { launch_fs<256, 0, true>(s, a, 0); }
+
+int attention_prefill_splits(const AttnArgs& a) {
+    int tps = 0;
+    return fs_plan(a, 256, 4 * 16, 0, &tps);
 }
 
 void attention_prefill(hipStream_t s, int head_dim, const AttnArgs& a) {

@@ -208,6 +208,17 @@ struct AttnArgs {
     const int* klen;
 };
 void attention_prefill(hipStream_t s, int head_dim, const AttnArgs& a);
+// prefix-LM prefill (head dim 256, klen set): query position j of batch row b attends keys [0, min(klen[b],
+// kv_start + max(pfx[b], j + 1))) -- the kv_start cached rows and the row's prefix (pfx, a device array indexed like
+// klen) from everywhere, the rest causally.  The argument of the one-pass key-split kernel's prefix instances alone:
+// every other attention kernel takes AttnArgs as it was
+struct AttnPrefixArgs : AttnArgs {
+    const int* pfx;
+    int kv_start;
+};
+void attention_prefill_prefix(hipStream_t s, const AttnPrefixArgs& a);
+// the key ranges the one-pass key-split kernel takes for a ragged or prefix call of these arguments (head dim 256)
+int attention_prefill_splits(const AttnArgs& a);
 // decode: Lq == 1, rows = the G heads; keys split over chunks; kv length from StepState (+1)
 // flash-decoding over 64-key chunks (partials only; the combine is gemv_o_attn's prologue);
 // launch_keys = upper bound on kv_len+1 this call

@@ -74,6 +74,7 @@ SIGNATURES = {
     "pgmi_decode": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp]),
     "pgmi_decode_steps": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
     "pgmi_lm_forward_ragged": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
+    "pgmi_lm_forward_prefix": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
     "pgmi_decode_ragged": (i32, [vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp]),
     "pgmi_decode_embeds": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp]),
     "pgmi_decode_embeds_dev": (i32, [vp, vp, i32, vp, i32, i32, i32, vp, i32, vp, i32, i64, vp, vp, i32, vp]),
@@ -144,6 +145,8 @@ SIGNATURES = {
     "pgmi_op_gemv_res": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     "pgmi_op_attention_ex": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, i32, i64, i64,
                                    i64, vp, vp]),
+    "pgmi_op_attention_prefix": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp]),
+    "pgmi_op_attention_prefix_splits": (i32, [vp, i32, i32, i32, i32, i32]),
     "pgmi_op_rope": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp]),
     "pgmi_op_scale": (i32, [vp, vp, f32, i64, vp, vp]),
 }

@@ -10,9 +10,11 @@ import ctypes
 import math
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _native as N
+from . import prefix_np as PX
 from . import ragged as R
 
 
@@ -54,6 +56,14 @@ class Score(NamedTuple):
     sums: torch.Tensor
     counts: torch.Tensor
     loss: torch.Tensor
+
+
+class CandidateScores(NamedTuple):
+    """Engine.score_candidates' result: each candidate's summed log-probability and token count, and its per-token
+    log-probabilities (a list of 1-D tensors, one per candidate)."""
+    sums: torch.Tensor
+    counts: torch.Tensor
+    logprobs: list
 
 
 class Engine:
@@ -343,7 +353,7 @@ class Engine:
         return out
 
     def lm_forward(self, kv: torch.Tensor, kv_start: int, positions, ids=None, image_feats=None, embeds=None,
-                   logits_rows: int = 0, lens=None) -> torch.Tensor:
+                   logits_rows: int = 0, lens=None, prefix_lens=None) -> torch.Tensor:
         """GemmaForCausalLM.forward over merged embeddings (see pgmi.h).  Returns fp32 logits
         (B, L, V) (logits_rows 0) or (B, 1, V): logits_rows 1 keeps every row's final hidden state
         for final_hidden / lazy all-row logits; 2 needs only the last row's, so the last layer's
@@ -351,8 +361,15 @@ class Engine:
 
         lens (B ints, optional): a ragged batch -- row b's tokens are ids[b, :lens[b]], the rest of the
         row is right padding (pgmi_lm_forward_ragged): each row attends its own real tokens only, pad
-        ids are never looked up, and logits_rows 1 / 2 return each row's logits at token lens[b] - 1."""
+        ids are never looked up, and logits_rows 1 / 2 return each row's logits at token lens[b] - 1.
+
+        prefix_lens (B ints, optional): the prefix-LM form (pgmi_lm_forward_prefix; the rule is pgmi.prefix_np's).
+        Token j of row b attends keys [0, kv_start + max(prefix_lens[b], j + 1)): its prefix from everywhere, the
+        tokens after it causally.  Positions stay the caller's (prefix_np.prefix_positions for the reference's
+        gap).  Token ids only; the call is eager (no prefill graph is looked up, captured or replayed)."""
         self._ready()
+        if prefix_lens is not None and embeds is not None:
+            raise ValueError("lm_forward: the prefix form (prefix_lens) takes token ids, not embeds")
         if lens is not None and embeds is not None:
             raise ValueError("lm_forward: a ragged batch (lens) takes token ids, not embeds")
         if embeds is not None:
@@ -373,10 +390,21 @@ class Engine:
         pos = torch.broadcast_to(pos.reshape(pos.shape[0] if pos.dim() > 1 else 1, -1), (B, L)).contiguous()
         V = self.cfgd["t_vocab"]
         out = torch.empty((B, L if logits_rows == 0 else 1, V), dtype=torch.float32, device=self.device)
+        ln = None
         if lens is not None:
             ln = torch.as_tensor(lens).detach().to("cpu", torch.int32).reshape(-1).contiguous()
             if ln.numel() != B:
                 raise ValueError(f"lens has {ln.numel()} entries for a batch of {B}")
+        if prefix_lens is not None:
+            pl = torch.as_tensor(prefix_lens).detach().to("cpu", torch.int32).reshape(-1).contiguous()
+            if pl.numel() != B:
+                raise ValueError(f"prefix_lens has {pl.numel()} entries for a batch of {B}")
+            N.check(self.lib.pgmi_lm_forward_prefix(self.ctx, idp, imgp, nimg, B, L, pos.data_ptr(), N.ptr(ln),
+                                                    pl.data_ptr(), kv.data_ptr(), kv.shape[2], kv.shape[3], kv_start,
+                                                    out.data_ptr(), logits_rows, self._s()),
+                    "pgmi_lm_forward_prefix")
+            return out
+        if ln is not None:
             N.check(self.lib.pgmi_lm_forward_ragged(self.ctx, idp, imgp, nimg, None, B, L, pos.data_ptr(),
                                                     ln.data_ptr(), kv.data_ptr(), kv.shape[2], kv.shape[3], kv_start,
                                                     out.data_ptr(), logits_rows, self._s()),
@@ -454,7 +482,8 @@ class Engine:
 
     @torch.no_grad()
     def score(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor], labels: torch.Tensor,
-              attention_mask: Optional[torch.Tensor] = None, ignore_index: int = -100, adapter=_KEEP) -> "Score":
+              attention_mask: Optional[torch.Tensor] = None, ignore_index: int = -100, adapter=_KEEP,
+              prefix_lens=None, image_feats: Optional[torch.Tensor] = None) -> "Score":
         """The reference's forward(labels=...) loss (modeling_gemma.py:596-603) per token, from one prefill:
         position j is scored against labels[:, j + 1], and only the rows whose shifted label is live go through
         the lm_head (one index_select on the final-normed rows, one host sync; no (B, L, V) tensor exists).
@@ -462,7 +491,18 @@ class Engine:
         attention_mask (B, L) of 0 / 1: a ragged batch as Engine.generate takes it; ids and labels are moved to
         the right-padded form and pad positions count as ignored whatever their label.  pixel_values None: a
         text-only prompt.  adapter: as generate's.  Returns Score(logprobs (B, L - 1) fp32 with 0 where ignored,
-        sums (B,), counts (B,), loss = -mean over the live tokens, NaN when there is none)."""
+        sums (B,), counts (B,), loss = -mean over the live tokens, NaN when there is none).
+
+        The default reproduces the reference's non-causal forward(labels=): every token attends every token, so a
+        teacher-forced answer is scored with its own tokens in view -- score an answer with prefix_lens.
+        prefix_lens (B ints): row b's first prefix_lens[b] real tokens (counted after right-padding, image tokens
+        included) are the prompt, attended from everywhere; the tokens after them attend causally and take the
+        positions the decode loop would give them (prefix_np.prefix_positions), so the log-probabilities are the
+        ones generate(return_logprobs=True) reports for the same tokens.  Labels of positions < prefix_lens[b] stay
+        the caller's business (mask them with ignore_index to score the answer alone).  image_feats: the projected
+        features, in place of pixel_values (score_candidates runs the vision tower once)."""
+        if image_feats is not None and pixel_values is not None:
+            raise ValueError("score: pixel_values or image_feats, not both")
         if adapter is not _KEEP:
             self.set_lora(adapter)
         ids = input_ids.to(self.device, torch.int64)
@@ -475,9 +515,16 @@ class Engine:
             lab, _ = R.right_pad(lab, attention_mask, pad_id=ignore_index)
         ids = ids.contiguous()
         B, L = ids.shape
-        feats = self.project(self.vision(pixel_values)) if pixel_values is not None else None
+        feats = self.project(self.vision(pixel_values)) if pixel_values is not None else image_feats
         kv = self.scratch_kv(B, L)
-        self.lm_forward(kv, 0, torch.arange(L).expand(B, L), ids=ids, image_feats=feats, logits_rows=1, lens=lens)
+        if prefix_lens is None:
+            self.lm_forward(kv, 0, torch.arange(L).expand(B, L), ids=ids, image_feats=feats, logits_rows=1, lens=lens)
+        else:
+            pl = np.asarray(torch.as_tensor(prefix_lens).detach().cpu(), dtype=np.int64).reshape(-1)
+            if pl.shape[0] != B:
+                raise ValueError(f"prefix_lens has {pl.shape[0]} entries for a batch of {B}")
+            self.lm_forward(kv, 0, torch.from_numpy(PX.prefix_positions(L, pl)), ids=ids, image_feats=feats,
+                            logits_rows=1, lens=lens, prefix_lens=pl)
         hidden = self.final_hidden(B * L)
         shift = lab[:, 1:]
         live = shift != ignore_index
@@ -485,6 +532,43 @@ class Engine:
             live &= (torch.arange(1, L, device=self.device)[None, :] < lens.to(self.device)[:, None])
         out, live, loss = self.shifted_logprobs(hidden, shift, live, ignore_index)
         return Score(out, out.sum(1), live.sum(1), loss)
+
+    @torch.no_grad()
+    def score_candidates(self, prompt_ids, pixel_values: Optional[torch.Tensor], candidates, adapter=_KEEP,
+                         ignore_index: int = -100) -> "CandidateScores":
+        """Rank candidate answers to one prompt: log p(candidate | image, prompt) for each of `candidates` (a list
+        of non-empty token lists) after prompt_ids (L0 tokens, image tokens included; 1-D or (1, L0)) and
+        pixel_values (one image, or None).  The vision tower and the projector run once and the features are
+        repeated per row; the rows prompt + candidate go through score(prefix_lens=L0) in groups of at most
+        max_batch, right-padded, with only the candidate's tokens labelled.  Returns CandidateScores(sums (C,) fp32,
+        counts (C,), logprobs: a list of C fp32 tensors, one value per candidate token)."""
+        if adapter is not _KEEP:
+            self.set_lora(adapter)
+        prompt = [int(t) for t in torch.as_tensor(prompt_ids).reshape(-1).tolist()]
+        cands = [[int(t) for t in c] for c in candidates]
+        L0 = len(prompt)
+        if L0 < 1 or not cands or any(len(c) < 1 for c in cands):
+            raise ValueError("score_candidates: a prompt and at least one candidate, none of them empty")
+        feats = self.project(self.vision(pixel_values)) if pixel_values is not None else None
+        if feats is not None and feats.shape[0] != 1:
+            raise ValueError("score_candidates takes one image")
+        sums, counts, per = [], [], []
+        for c0 in range(0, len(cands), self.max_batch):
+            grp = cands[c0:c0 + self.max_batch]
+            B, L = len(grp), L0 + max(len(c) for c in grp)
+            ids = torch.zeros((B, L), dtype=torch.int64)
+            lab = torch.full((B, L), ignore_index, dtype=torch.int64)
+            mask = torch.zeros((B, L), dtype=torch.int64)
+            for b, c in enumerate(grp):
+                ids[b, :L0 + len(c)] = torch.tensor(prompt + c)
+                lab[b, L0:L0 + len(c)] = torch.tensor(c)
+                mask[b, :L0 + len(c)] = 1
+            sc = self.score(ids, None, lab, attention_mask=mask, ignore_index=ignore_index, prefix_lens=[L0] * B,
+                            image_feats=feats.expand(B, -1, -1) if feats is not None else None)
+            sums.append(sc.sums)
+            counts.append(sc.counts)
+            per += [sc.logprobs[b, L0 - 1:L0 - 1 + len(c)] for b, c in enumerate(grp)]
+        return CandidateScores(torch.cat(sums), torch.cat(counts), per)
 
     def decode(self, ids: torch.Tensor, kv: torch.Tensor, kv_len: int, position: int, logits: torch.Tensor = None,
                next_ids: torch.Tensor = None, graph: bool = False) -> torch.Tensor:
