@@ -94,17 +94,28 @@ struct TextLayerW {
     const uint16_t *qkv, *o, *gate_up, *down, *in_norm, *post_norm;
     // batched decode (B >= 3): this layer's fragment-major images (ensure_mf_image), null while the image is absent
     const uint16_t *mf_gate_up = nullptr, *mf_qkv = nullptr, *mf_o = nullptr, *mf_down = nullptr;
-    // decode at B <= 2: the 13-bit images of gate|up and down (ensure_pk_image), img null while absent or raw
-    PkW pk_gate_up, pk_down;
-    // batched decode (B >= 3): the fragment-major 13-bit images of the same two (ensure_pk_image_mf)
-    PkW pkb_gate_up, pkb_down;
+    // the 13-bit images of gate|up and down by form (PkForm: row-major segments for B <= 2, fragment-major ones for
+    // B >= 3; ensure_pk_image), img null while absent or raw
+    PkW pk_gate_up[2], pk_down[2];
 };
 struct WeightTable {
     const uint16_t *patch_conv_w, *patch_b, *pos_emb, *post_ln_w, *post_ln_b, *proj_w, *proj_b, *embed, *final_norm;
     std::vector<VisionLayerW> v;
     std::vector<TextLayerW> t;
-    PkW pk_embed;  // the tied embedding's 13-bit image as lm_head reads it (the raw rows stay for look-up and prefill)
-    PkW pkb_embed;  // its fragment-major 13-bit image (the batched lm_head), rows padded to a whole 16-row group
+    // the tied embedding's 13-bit images as lm_head reads them, by form (the raw rows stay for look-up and prefill;
+    // the fragment-major form's rows are padded to a whole 16-row group)
+    PkW pk_embed[2];
+};
+
+// The 13-bit images (pack13.h) of one form: every layer's gate|up and down rows and the tied embedding, one buffer per
+// kind (PK_GATE_UP, PK_DOWN, PK_LM_HEAD); built by ensure_pk_image, read through w.t[i].pk_*[form] / w.pk_embed[form].
+// mask: the kinds a step of that form reads packed (row form: pgmi_set_decode_packed, < 0 the per-batch default,
+// pk_mask_for; fragment form: pgmi_set_decode_packed_batched, never negative); done: the kinds scanned (and packed,
+// where they fit) or given up since the last pgmi_prepare; alloc_failed: a kind's buffer could not be allocated
+struct PkImages {
+    uint8_t* buf[3];
+    int mask, done;
+    bool alloc_failed;
 };
 
 // weight kinds with a 13-bit image (bits of pgmi_set_decode_packed's mask)
@@ -167,20 +178,11 @@ struct pgmi_ctx {
     uint16_t* mfw = nullptr;
     bool mfw_dirty = false;  // the fragment-major images are (re)built by the next batched decode step
     bool mfw_alloc_failed = false;  // their allocation failed: the batched decode reads the row-major weights
-    // decode at B <= 2: 13-bit images (pack13.h) of every layer's gate|up and down rows and of the tied embedding,
-    // one buffer per kind (PK_GATE_UP, PK_DOWN, PK_LM_HEAD); built by ensure_pk_image, read through w.t[i].pk_* /
-    // w.pk_embed.  pk_mask: the kinds the step reads packed (pgmi_set_decode_packed; < 0: the per-batch default,
-    // pk_mask_for); pk_done: the kinds scanned (and packed, where they fit) or given up since the last pgmi_prepare
-    uint8_t* pk_buf[3] = {nullptr, nullptr, nullptr};
+    // the 13-bit images by form: [PK_FORM_ROWS] decode at B <= 2 (default mask: per batch), [PK_FORM_FRAG] batched
+    // decode at B >= 3 (default: none; with every kind on up to 3.80 GB beside mfw at the 3B shapes).  pk_stat: the
+    // scan results of a build, shared
+    PkImages pk[2] = {{{nullptr, nullptr, nullptr}, -1, 0, false}, {{nullptr, nullptr, nullptr}, 0, 0, false}};
     unsigned* pk_stat = nullptr;
-    int pk_mask = -1, pk_done = 0;
-    bool pk_alloc_failed = false;
-    // batched decode (B >= 3): the fragment-major 13-bit images of the same tensors (pack13.h), buffers of their
-    // own; pk_mask_batched: the kinds the batched step reads packed (pgmi_set_decode_packed_batched, default none);
-    // pk_done_batched: as pk_done.  Built by ensure_pk_image_mf, read through w.t[i].pkb_* / w.pkb_embed
-    uint8_t* pkb_buf[3] = {nullptr, nullptr, nullptr};
-    int pk_mask_batched = 0, pk_done_batched = 0;
-    bool pkb_alloc_failed = false;
     float *opart, *pmax, *dlogits, *amax_v;
     int *pidx, *amax_i;
     int max_chunks;
@@ -223,19 +225,26 @@ struct pgmi_ctx {
 
 namespace pgmi_eng __attribute__((visibility("hidden"))) {
 
-// the kinds a B-row step reads packed: the caller's mask, or the measured default of that batch size
+// the form a B-row step's GEMVs read: row-major segments (the streaming forms) or fragment-major ones (the MFMA forms)
+inline PkForm pk_form_of(int B) { return B >= gemv_mf_min_batch() ? PK_FORM_FRAG : PK_FORM_ROWS; }
+
+// the kinds a B-row step reads packed: the caller's mask for B's form, or (row form) the measured default of that
+// batch size
 inline int pk_mask_for(const pgmi_ctx* x, int B) {
-    return x->pk_mask >= 0 ? x->pk_mask : B <= 1 ? kPkDefaultB1 : kPkDefaultB2;
+    const int mask = x->pk[pk_form_of(B)].mask;
+    return mask >= 0 ? mask : B <= 1 ? kPkDefaultB1 : kPkDefaultB2;
 }
 
-// the image a B-row decode GEMV of `kind` reads now: w (B <= 2, the streaming forms) or *wb (B >= 3, the MFMA
-// forms' fragment-major image), or none (the bf16 weights) while the kind is switched off for that batch, not
-// built since the last pgmi_prepare, or the tensor did not fit (img null).  wb null: the caller has no batched
-// packed form (the prefill's last-row GEMVs launch at B >= 3 what they always did).
-inline PkW pk_use(const pgmi_ctx* x, int B, int kind, const PkW& w, const PkW* wb = nullptr) {
-    if (B >= gemv_mf_min_batch()) return wb && (x->pk_mask_batched & x->pk_done_batched & kind) ? *wb : PkW{};
-    const bool on = B <= 2 && (pk_mask_for(x, B) & x->pk_done & kind);
-    return on ? w : PkW{};
+// the image a B-row decode GEMV of `kind` reads now: w[form of B], or none (the bf16 weights) while the kind is
+// switched off for that batch, not built since the last pgmi_prepare, or the tensor did not fit (img null).
+inline PkW pk_use(const pgmi_ctx* x, int B, int kind, const PkW (&w)[2]) {
+    const PkForm f = pk_form_of(B);
+    return (pk_mask_for(x, B) & x->pk[f].done & kind) ? w[f] : PkW{};
+}
+// the same for a caller with no batched packed form: the prefill's last-row GEMVs (lm_last_row_tail, lm_logits),
+// which at B >= 3 launch the bf16 weights whatever the fragment form's state (its changes do not drop their graphs)
+inline PkW pk_use_rows(const pgmi_ctx* x, int B, int kind, const PkW (&w)[2]) {
+    return pk_form_of(B) == PK_FORM_ROWS ? pk_use(x, B, kind, w) : PkW{};
 }
 
 // does this context's batched decode (B >= 3) read fragment-major images at all
@@ -298,8 +307,8 @@ int ensure_prepared(pgmi_ctx* x);
 void pk_forget(pgmi_ctx* x);
 void pk_forget_kinds(pgmi_ctx* x, int kinds);
 int ensure_mf_image(pgmi_ctx* x, hipStream_t s);
-int ensure_pk_image(pgmi_ctx* x, hipStream_t s, int B);
-int ensure_pk_image_mf(pgmi_ctx* x, hipStream_t s);
+int ensure_pk_image(pgmi_ctx* x, hipStream_t s, int B);      // the 13-bit images of B's form
+int ensure_decode_images(pgmi_ctx* x, hipStream_t s, int B);  // what a B-row decode step reads: mfw, then those
 // engine_lora.hip
 void lora_forget_pristine(pgmi_ctx* x);
 // engine_prefill.hip: what a prefill does before its launches, then the stages of one row group (PrefillRun) --

@@ -14,25 +14,24 @@ int pgmi_decode_kernel(pgmi_ctx* x, int which, int layer, int B, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const float eps = c.t_rms_eps;
     const int H = c.t_hidden;
-    // which 2, 3 and 4 read what the decode step reads: the 13-bit images at B <= 2 (pgmi_set_decode_packed)
-    // (pgmi_set_decode_packed_batched at B >= 3)
-    if (which >= 2 && B < gemv_mf_min_batch() && (rc = ensure_pk_image(x, s, B))) return rc;
-    if (which >= 2 && B >= gemv_mf_min_batch() && (rc = ensure_pk_image_mf(x, s))) return rc;
+    // which 2, 3 and 4 read what the decode step reads: the 13-bit images of B's form (pgmi_set_decode_packed at
+    // B <= 2, pgmi_set_decode_packed_batched at B >= 3); not the bf16 fragment-major image, which they do not pass
+    if (which >= 2 && (rc = ensure_pk_image(x, s, B))) return rc;
     const TextLayerW& w = x->w.t[layer];
     switch (which) {
         case 1: gemv_res(s, B, c.t_heads * c.t_head_dim, x->dAO, w.o, H, x->dH, x->ws); break;
         case 2:
             gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
-                       pk_use(x, B, PK_GATE_UP, w.pk_gate_up, &w.pkb_gate_up));
+                       pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
             break;
         case 3:
             gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws,
-                     pk_use(x, B, PK_DOWN, w.pk_down, &w.pkb_down));
+                     pk_use(x, B, PK_DOWN, w.pk_down));
             break;
         case 4: {
             int nparts = 0;
             gemv_logits(s, B, x->dH, x->w.final_norm, eps, x->w.embed, c.t_vocab, x->dlogits, x->pmax, x->pidx,
-                        &nparts, nullptr, nullptr, nullptr, nullptr, 1, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed, &x->w.pkb_embed));
+                        &nparts, nullptr, nullptr, nullptr, nullptr, 1, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed));
             break;
         }
         default: return fail(PGMI_E_ARG, "unknown kernel id");
@@ -67,9 +66,7 @@ int pgmi_debug_decode_stage(pgmi_ctx* x, int stage, int layer, int B, const int6
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIPCHK(hipStreamIsCapturing(s, &cap));
     if (cap != hipStreamCaptureStatusNone) return fail(PGMI_E_STATE, "pgmi_debug_decode_stage inside a stream capture");
-    if (B >= gemv_mf_min_batch() && (rc = ensure_mf_image(x, s))) return rc;
-    if (B >= gemv_mf_min_batch() && (rc = ensure_pk_image_mf(x, s))) return rc;
-    if (B < gemv_mf_min_batch() && (rc = ensure_pk_image(x, s, B))) return rc;
+    if ((rc = ensure_decode_images(x, s, B))) return rc;
     // the step record(s) are set by every call (and so restored after stage 5, whose last kernel advances
     // them); the decode entry points set theirs again afterwards
     const auto set_records = [&]() {

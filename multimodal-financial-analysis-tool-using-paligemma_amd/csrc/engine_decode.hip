@@ -84,19 +84,19 @@ void decode_layer(const pgmi_ctx* x, const DecodeRun& r, int i, int stage) {
         // normalises h on load (no k_rows_norm pass: B = 8 step -5 us per layer)
         if (on(3))
             gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, x->dSS, w.mf_gate_up,
-                       pk_use(x, B, PK_GATE_UP, w.pk_gate_up, &w.pkb_gate_up));
+                       pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
         if (on(4))
             gemv_res_norm(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws,
                           i + 1 < c.t_layers ? x->w.t[i + 1].in_norm : nullptr, eps, x->dHn, w.mf_down,
-                          pk_use(x, B, PK_DOWN, w.pk_down, &w.pkb_down));
+                          pk_use(x, B, PK_DOWN, w.pk_down));
         return;
     }
     if (on(3))
         gemv_geglu(s, B, x->dH, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
-                   pk_use(x, B, PK_GATE_UP, w.pk_gate_up, &w.pkb_gate_up));
+                   pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
     if (on(4))
         gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, x->dH, x->ws,
-                 pk_use(x, B, PK_DOWN, w.pk_down, &w.pkb_down));
+                 pk_use(x, B, PK_DOWN, w.pk_down));
 }
 
 // final norm + lm_head + argmax.  The step's last work also advances the device step state (pgmi_decode
@@ -108,7 +108,7 @@ void decode_tail(const pgmi_ctx* x, const DecodeRun& r, float* logits, int64_t* 
     int nparts = 0;
     int64_t* nx = next_ids ? next_ids : x->d_next;
     if (!gemv_logits(r.s, r.B, x->dH, x->w.final_norm, c.t_rms_eps, x->w.embed, c.t_vocab, logits, x->pmax, x->pidx,
-                     &nparts, x->lm_done, nx, st, hist, adv_n, pk_use(x, r.B, PK_LM_HEAD, x->w.pk_embed, &x->w.pkb_embed)))
+                     &nparts, x->lm_done, nx, st, hist, adv_n, pk_use(x, r.B, PK_LM_HEAD, x->w.pk_embed)))
         argmax_finish(r.s, r.B, x->pmax, x->pidx, nparts, nx, st, hist, adv_n);
 }
 
@@ -169,9 +169,7 @@ static int decode_step(pgmi_ctx* x, const int64_t* ids, const void* embeds, int 
     if (kv_max > c.max_kv) return fail(PGMI_E_ARG, "kv_max exceeds config max_kv");
     if ((!ids && !embeds) || !kv || !logits) return fail(PGMI_E_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;
-    if (B >= gemv_mf_min_batch() && (rc = ensure_mf_image(x, s))) return rc;
-    if (B >= gemv_mf_min_batch() && (rc = ensure_pk_image_mf(x, s))) return rc;
-    if (B < gemv_mf_min_batch() && (rc = ensure_pk_image(x, s, B))) return rc;
+    if ((rc = ensure_decode_images(x, s, B))) return rc;
     int masked = 0;
     if (dev) {
         // position read on the device; the host no longer knows it, so the next call sets the state again

@@ -21,20 +21,17 @@
 //      w (slab pointers)         bind_tables <- pgmi_bind_weights                         all
 //      w.t[i].mf_*, mfw          ensure_mf_image, when it allocates the images            decode, small and batched
 //                                (a rebuild after pgmi_prepare / pgmi_lora_set is in place: same pointers)
-//      w.t[i].pk_*, w.pk_embed,  ensure_pk_image, when it changed pk_done                 decode B <= 2, prefill
-//      pk_done                   pk_forget <- pgmi_bind_weights, pgmi_prepare             all
-//                                pk_forget_kinds <- pgmi_lora_set                         decode B <= 2, prefill
-//      pk_mask                   pgmi_set_decode_packed                                   decode B <= 2, prefill
-//      w.t[i].pkb_*, w.pkb_embed, ensure_pk_image_mf, when it changed pk_done_batched     decode B >= 3
-//      pk_done_batched           pk_forget <- pgmi_bind_weights, pgmi_prepare             all
-//                                pk_forget_kinds <- pgmi_lora_set (gate / up / down)      decode B >= 3
-//      pk_mask_batched           pgmi_set_decode_packed_batched                           decode B >= 3
+//      (the 13-bit images, per form f; pk_graphs(f): rows -> decode B <= 2, prefill; fragment -> decode B >= 3)
+//      w.t[i].pk_*[f],           ensure_pk_image, when it changed pk[f].done              pk_graphs(f)
+//      w.pk_embed[f], pk[f].done pk_forget <- pgmi_bind_weights, pgmi_prepare             all
+//                                pk_forget_kinds <- pgmi_lora_set (gate / up / down)      pk_graphs(f), where f had one done
+//      pk[f].mask                pgmi_set_decode_packed (rows) / _batched (fragment)      pk_graphs(f)
 //      mf_staged                 pgmi_set_decode_staged_norm                              decode, small and batched
 //      probe_on, probe_ev        pgmi_prefill_probe (prefill graphs are off while on)     prefill
 //      prefill_graph             pgmi_set_prefill_graph, pgmi_prefill_probe               prefill
 //      everything                pgmi_prepare, pgmi_destroy                               all
 //    The prefill reads the 13-bit images too: a last-row-only prefill (logits_rows 2) and every lm_head over last
-//    rows run the decode GEMVs, which pk_use switches by pk_mask and pk_done.
+//    rows run the decode GEMVs, which pk_use switches by the row form's mask and done (never the fragment form's).
 //
 // 4. What each call rewrites outside the graph, before it: the positions (dpos, lm_begin), a ragged prefill's row
 //    lengths (d_rlens, lm_begin), the step records (step / rstep: set when the call does not continue the last
@@ -72,6 +69,10 @@ namespace pgmi_eng __attribute__((visibility("hidden"))) {
 // read the 13-bit images), those of more rows
 enum { GRAPHS_PREFILL = 1, GRAPHS_DECODE_SMALL = 2, GRAPHS_DECODE_BATCHED = 4,
        GRAPHS_DECODE = GRAPHS_DECODE_SMALL | GRAPHS_DECODE_BATCHED, GRAPHS_ALL = GRAPHS_PREFILL | GRAPHS_DECODE };
+
+// the graphs whose launches hold a form's 13-bit images (or their absence): the B <= 2 steps and the prefill's
+// last-row GEMVs read the row form, the batched steps the fragment form
+inline int pk_graphs(PkForm f) { return f == PK_FORM_FRAG ? GRAPHS_DECODE_BATCHED : GRAPHS_DECODE_SMALL | GRAPHS_PREFILL; }
 
 // A prefill key: the kind of call (1 vision tower, 2 language-model forward), its arguments, the tuning epoch.
 inline std::vector<intptr_t> prefill_key(int kind, std::initializer_list<intptr_t> args) {

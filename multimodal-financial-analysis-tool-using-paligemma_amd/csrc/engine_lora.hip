@@ -197,11 +197,12 @@ int pgmi_lora_set(pgmi_ctx* x, int id, void* stream) {
         if (ends_with(nm, "mlp.gate_proj.weight") || ends_with(nm, "mlp.up_proj.weight")) kinds |= PK_GATE_UP;
         if (ends_with(nm, "mlp.down_proj.weight")) kinds |= PK_DOWN;
     }
-    if (kinds & (x->pk_done | x->pk_done_batched)) {
-        // captured steps hold the old images' launches (packed or raw, exponent base); a last-row-only prefill's GEMVs
-        // likewise, for the B <= 2 images; the batched step's for the fragment-major ones
-        const int drop = ((kinds & x->pk_done) ? GRAPHS_DECODE_SMALL | GRAPHS_PREFILL : 0) |
-                         ((kinds & x->pk_done_batched) ? GRAPHS_DECODE_BATCHED : 0);
+    // captured steps hold the old images' launches (packed or raw, exponent base), each form's in the graphs that read
+    // it (pk_graphs)
+    int drop = 0;
+    for (int f = 0; f < 2; ++f)
+        if (kinds & x->pk[f].done) drop |= pk_graphs((PkForm)f);
+    if (drop) {
         pk_forget_kinds(x, kinds);
         graphs_drop(x, drop);
     }

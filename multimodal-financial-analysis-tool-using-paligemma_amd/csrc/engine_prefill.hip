@@ -229,8 +229,9 @@ int lm_last_row_tail(const pgmi_ctx* x, const PrefillRun& r, int i) {
         gemv_res(s, B, NH * HD, x->dAO, w.o, H, lastrows, x->ws);
     }
     gemv_geglu(s, B, lastrows, w.post_norm, eps, w.gate_up, c.t_intermediate, x->dACT, nullptr, nullptr,
-               pk_use(x, B, PK_GATE_UP, w.pk_gate_up));
-    gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, lastrows, x->ws, pk_use(x, B, PK_DOWN, w.pk_down));
+               pk_use_rows(x, B, PK_GATE_UP, w.pk_gate_up));
+    gemv_res(s, B, c.t_intermediate, x->dACT, w.down, H, lastrows, x->ws,
+             pk_use_rows(x, B, PK_DOWN, w.pk_down));
     return 0;
 }
 
@@ -255,7 +256,7 @@ int lm_logits(const pgmi_ctx* x, const PrefillRun& r) {
                                     (size_t)H * 2, B, hipMemcpyDeviceToDevice, s));
         int nparts = 0;
         gemv_logits(s, B, lastrows, x->w.final_norm, c.t_rms_eps, E, c.t_vocab, logits, x->pmax, x->pidx, &nparts,
-                    nullptr, nullptr, nullptr, nullptr, 1, pk_use(x, B, PK_LM_HEAD, x->w.pk_embed));
+                    nullptr, nullptr, nullptr, nullptr, 1, pk_use_rows(x, B, PK_LM_HEAD, x->w.pk_embed));
     }
     return 0;
 }

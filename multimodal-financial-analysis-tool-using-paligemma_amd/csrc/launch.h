@@ -118,17 +118,17 @@ void gemv_qkv(hipStream_t s, int B, int nh, int nkv, const uint16_t* h, const ui
               int st_stride = 0);
 // The 13-bit image of a weight matrix (pack13.h) for the streaming GEMVs at B <= 2 (gate|up, down at K = 16384,
 // lm_head): img null = read the bf16 rows; base2 = pk_base2(e_hi).  Same outputs, bit for bit, either way.
-// At B >= gemv_mf_min_batch() the same arguments take the fragment-major image (pk_pack_mf) for the MFMA forms.
+// At B >= gemv_mf_min_batch() the same arguments take the image's fragment-major form (PK_FORM_FRAG) for the MFMA
+// forms.  A launcher is handed the image of the form its batch reads (pk_use), never both.
 struct PkW {
     const uint8_t* img = nullptr;
     unsigned base2 = 0;
 };
 // pass one / two of the image build (kernels_pack.hip): stat[0] = largest exponent field, stat[1] = smallest
-// one >= 1 (caller presets 0 / 0xFFFFFFFF); out: pk_image_bytes(rows, K) bytes, K a multiple of 2048
+// one >= 1 (caller presets 0 / 0xFFFFFFFF); form: a PkForm (pack13.h) -- row-major segments for the streaming GEMVs
+// (B <= 2), fragment-major ones for the MFMA GEMVs; out: pk_image_bytes(form, rows, K) bytes, K a multiple of 2048
 void pk_scan(hipStream_t s, const uint16_t* W, long numel, unsigned* stat);
-void pk_pack(hipStream_t s, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out);
-// the fragment-major image the batched (B >= 3) MFMA GEMVs read (pack13.h): pk_image_bytes_mf(rows, K) bytes
-void pk_pack_mf(hipStream_t s, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out);
+void pk_pack(hipStream_t s, int form, const uint16_t* W, long rows, int K, int e_hi, uint8_t* out);
 // LoRA (kernels_lora.hip, the rule of lora.h): out[N][K] = bf16(W + (B . A) * scaling) from the pristine W (bf16),
 // A[r][K] and B[N][r] in fp32 (all 16-B aligned, K a multiple of 8, r in [1, 256]); out does not overlap W.  lora_widen:
 // n factor values of dtype PGMI_DTYPE_* on the device to fp32.

@@ -28,6 +28,9 @@
 // four B fragments k_gemv_mf's issue loads for k block kb.  Segments follow the fragment-major bf16 image: segment
 // gr * (K / 128) + kb over the ceil(rows / 16) groups (gate|up as one 2 I x H matrix: the up rows' groups after the
 // gate rows').  Rows past the last one are encoded as zeros (exponent field 0, u = 0); their results are never stored.
+//
+// The two forms differ in the gather alone (PkForm, pk_segs, pk_src below); the record, its four pieces and their
+// offsets in a segment are common.
 #include "common.h"
 
 namespace pgmi {
@@ -114,8 +117,6 @@ PK_HD int pk_off_b(int l) { return 1024 + 16 * l; }
 PK_HD int pk_off_n(int l) { return 2048 + 16 * l; }
 PK_HD int pk_off_h(int l) { return 3072 + 4 * l; }
 
-inline int64_t pk_image_bytes(int64_t rows, int64_t K) { return rows * (K / kPkSegK) * kPkSegBytes; }
-
 // ---- the fragment-major gather (16-row group x 128-k block per segment)
 constexpr int kPkMfRows = 16, kPkMfK = 128;
 
@@ -125,6 +126,67 @@ PK_HD int64_t pk_mf_seg(int64_t gr, int64_t kb, int64_t K) { return gr * (K / kP
 PK_HD int64_t pk_mf_row(int64_t gr, int l) { return kPkMfRows * gr + (l & 15); }
 PK_HD int64_t pk_mf_k(int64_t kb, int l, int c) { return kPkMfK * kb + 32 * c + 8 * (l >> 4); }
 
-inline int64_t pk_image_bytes_mf(int64_t rows, int64_t K) { return pk_mf_groups(rows) * (K / kPkMfK) * kPkSegBytes; }
+// ---- the two gathers, stated once: what differs between the forms is which weights a segment holds.  Everything
+// that builds or reads back an image (the pack kernel, the host encode / decode below) goes through these three.
+enum PkForm { PK_FORM_ROWS = 0, PK_FORM_FRAG = 1 };  // row-major segments (B <= 2), fragment-major ones (B >= 3)
+
+// the segments of the image of a [rows][K] matrix, and its bytes
+PK_HD int64_t pk_segs(PkForm f, int64_t rows, int64_t K) {
+    return f == PK_FORM_FRAG ? pk_mf_groups(rows) * (K / kPkMfK) : rows * (K / kPkSegK);
+}
+PK_HD int64_t pk_image_bytes(PkForm f, int64_t rows, int64_t K) { return pk_segs(f, rows, K) * kPkSegBytes; }
+
+// the element offset in W[rows][K] of the 8 weights at (segment seg, lane l, chunk c); >= rows * K: a pad row of
+// the fragment-major form's last group (encoded as zeros; a decode writes it, into a matrix of whole groups)
+PK_HD int64_t pk_src(PkForm f, int64_t seg, int l, int c, int64_t K) {
+    if (f == PK_FORM_ROWS) return seg * kPkSegK + 512 * c + 8 * l;
+    const int64_t kbs = K / kPkMfK;
+    return pk_mf_row(seg / kbs, l) * K + pk_mf_k(seg % kbs, l, c);
+}
+
+// lane l's record <-> its four pieces in the segment at seg (no alignment assumed: the host's images are a caller's)
+PK_HD void pk_put(uint8_t* seg, int l, const PkSeg& s) {
+    __builtin_memcpy(seg + pk_off_a(l), &s.a, 16);
+    __builtin_memcpy(seg + pk_off_b(l), &s.b, 16);
+    __builtin_memcpy(seg + pk_off_n(l), &s.n, 16);
+    __builtin_memcpy(seg + pk_off_h(l), &s.h, 4);
+}
+PK_HD PkSeg pk_get(const uint8_t* seg, int l) {
+    PkSeg s;
+    __builtin_memcpy(&s.a, seg + pk_off_a(l), 16);
+    __builtin_memcpy(&s.b, seg + pk_off_b(l), 16);
+    __builtin_memcpy(&s.n, seg + pk_off_n(l), 16);
+    __builtin_memcpy(&s.h, seg + pk_off_h(l), 4);
+    return s;
+}
+
+// The format on the host (tests, no device): the image of w[rows][K] and its decode, through the very functions the
+// kernels use.  The fragment-major decode writes pk_mf_groups(rows) * 16 rows (the pad rows decode to +0).
+template <PkForm F>
+inline void pk_encode_host(const uint16_t* w, int64_t rows, int64_t K, int e_hi, uint8_t* image) {
+    for (int64_t seg = 0; seg < pk_segs(F, rows, K); ++seg)
+        for (int l = 0; l < 64; ++l) {
+            uint4 f[4];
+            for (int c = 0; c < 4; ++c) {
+                const int64_t off = pk_src(F, seg, l, c, K);
+                f[c] = make_uint4(0, 0, 0, 0);
+                if (off < rows * K) __builtin_memcpy(&f[c], w + off, 16);
+            }
+            pk_put(image + seg * kPkSegBytes, l, pk_encode(f, e_hi));
+        }
+}
+
+template <PkForm F>
+inline void pk_decode_host(const uint8_t* image, int64_t rows, int64_t K, int e_hi, uint16_t* w) {
+    const unsigned b2 = pk_base2(e_hi);
+    for (int64_t seg = 0; seg < pk_segs(F, rows, K); ++seg)
+        for (int l = 0; l < 64; ++l) {
+            const PkSeg s = pk_get(image + seg * kPkSegBytes, l);
+            for (int c = 0; c < 4; ++c) {
+                const uint4 f = pk_chunk(s, c, b2);
+                __builtin_memcpy(w + pk_src(F, seg, l, c, K), &f, 16);
+            }
+        }
+}
 
 }  // namespace pgmi

@@ -693,46 +693,57 @@ class Engine:
         """Batched decode RMSNorm form: 0 once per row (default), 1 staged per projection, -1 default."""
         N.check(self.lib.pgmi_set_decode_staged_norm(self.ctx, int(on)), "pgmi_set_decode_staged_norm")
 
+    # The 13-bit weight images come in two forms with one C entry each: "" (row-major segments, batch 1-2) and
+    # "_batched" (fragment-major segments, 3..16 rows).  The six public methods below name the form; these do the call.
+    def _set_packed(self, form: str, mask: int) -> None:
+        name = f"pgmi_set_decode_packed{form}"
+        N.check(getattr(self.lib, name)(self.ctx, int(mask)), name)
+
+    def _packed_info(self, form: str, n: int):
+        name = f"pgmi_decode_packed{form}_info"
+        v = (ctypes.c_int64 * n)()
+        N.check(getattr(self.lib, name)(self.ctx, v, n), name)
+        return v
+
+    def _packed_tensor(self, form: str, kind: int, layer: int) -> bool:
+        name = f"pgmi_decode_packed{form}_tensor"
+        rc = getattr(self.lib, name)(self.ctx, int(kind), int(layer))
+        if rc < 0:
+            N.check(rc, name)
+        return rc == 1
+
     def set_decode_packed(self, on: int) -> None:
         """Decode at batch 1-2 on the lossless 13-bit weight images: 0 off, a mask of kinds (1 gate|up, 2 down,
         4 lm_head; 7 all), -1 the default (all at B = 1, lm_head at B = 2).  Results are bit-identical either way (pgmi_set_decode_packed)."""
-        N.check(self.lib.pgmi_set_decode_packed(self.ctx, int(on)), "pgmi_set_decode_packed")
+        self._set_packed("", on)
 
     def decode_packed_info(self) -> dict:
         """How the batch 1-2 decode step reads its 2 x layers + 1 streamed tensors now (pgmi_decode_packed_info)."""
-        v = (ctypes.c_int64 * 9)()
-        N.check(self.lib.pgmi_decode_packed_info(self.ctx, v, 9), "pgmi_decode_packed_info")
+        v = self._packed_info("", 9)
         return {"mask": v[0], "mask_b2": v[8], "packed": v[1], "raw": v[2], "packed_bytes": v[3], "raw_bytes": v[4],
                 "alloc_failed": bool(v[5]), "mf_alloc_failed": bool(v[6]), "scanned": v[7]}
 
     def decode_packed_tensor(self, kind: int, layer: int = 0) -> bool:
         """Is the tensor of kind 1 gate|up / 2 down (of `layer`) / 4 lm_head read from its 13-bit image now?"""
-        rc = self.lib.pgmi_decode_packed_tensor(self.ctx, int(kind), int(layer))
-        if rc < 0:
-            N.check(rc, "pgmi_decode_packed_tensor")
-        return rc == 1
+        return self._packed_tensor("", kind, layer)
 
     def set_decode_packed_batched(self, mask: int) -> None:
         """Batched decode (3..16 rows) on the fragment-major 13-bit weight images: 0 off (the default), or a mask of
         kinds (1 gate|up, 2 down, 4 lm_head; 7 all).  Results are bit-identical either way
         (pgmi_set_decode_packed_batched)."""
-        N.check(self.lib.pgmi_set_decode_packed_batched(self.ctx, int(mask)), "pgmi_set_decode_packed_batched")
+        self._set_packed("_batched", mask)
 
     def decode_packed_batched_info(self) -> dict:
         """How the batched decode step reads its 2 x layers + 1 streamed tensors now
         (pgmi_decode_packed_batched_info)."""
-        v = (ctypes.c_int64 * 6)()
-        N.check(self.lib.pgmi_decode_packed_batched_info(self.ctx, v, 6), "pgmi_decode_packed_batched_info")
+        v = self._packed_info("_batched", 6)
         return {"mask": v[0], "scanned": v[1], "packed": v[2], "raw": v[3], "packed_bytes": v[4],
                 "alloc_failed": bool(v[5])}
 
     def decode_packed_batched_tensor(self, kind: int, layer: int = 0) -> bool:
         """Is the tensor of kind 1 gate|up / 2 down (of `layer`) / 4 lm_head read from its fragment-major 13-bit
         image by the batched step now?"""
-        rc = self.lib.pgmi_decode_packed_batched_tensor(self.ctx, int(kind), int(layer))
-        if rc < 0:
-            N.check(rc, "pgmi_decode_packed_batched_tensor")
-        return rc == 1
+        return self._packed_tensor("_batched", kind, layer)
 
     def decode_kernel(self, which: int, layer: int, B: int) -> None:
         """One decode projection on the decode workspace (pgmi_decode_kernel): 1 o_proj, 2 gate|up, 3 down, 4 lm_head."""

@@ -124,6 +124,59 @@ def test_index_map_is_the_bf16_fragment_major_image():
     assert np.array_equal(np.sort((r * k + kk).reshape(-1)), np.arange(rows * k))
 
 
+def _read_back(img):
+    """(sign|mantissa byte, stored 5-bit value u = 31 - code) of every weight of an image's segments, each
+    [segments][64 lanes][4 chunks][8]: seg_image_np's byte layout (pgmi/packed.py) read the other way."""
+    seg = np.ascontiguousarray(img).reshape(-1, P.SEG_BYTES)
+    n = seg.shape[0]
+    sm = np.concatenate([seg[:, 0:1024].reshape(n, 64, 2, 8), seg[:, 1024:2048].reshape(n, 64, 2, 8)], axis=2)
+    j = np.arange(8)
+    nib = np.ascontiguousarray(seg[:, 2048:3072]).view("<u4").reshape(n, 64, 4)
+    low = (nib[..., None] >> (16 * (j & 1) + 4 * (j >> 1)).astype(np.uint32)) & 15
+    hi = np.ascontiguousarray(seg[:, 3072:3328]).view("<u4").reshape(n, 64)
+    c = np.arange(4)[:, None]
+    top = (hi[..., None, None] >> (16 * (j & 1)[None, :] + 4 * c + (j >> 1)[None, :]).astype(np.uint32)) & 1
+    return sm, (low | (top << 4)).astype(np.uint8)
+
+
+def test_both_forms_hold_the_same_record_of_every_weight():
+    """Same record, two gathers: one fitting 40 x 4096 matrix (a partial last group; two row-major segments per row,
+    32 k blocks) through both encoders.  Every weight's 13 bits -- its sign|mantissa byte and its stored 5-bit value
+    (u = 31 - code: what the planes hold) -- read back with numpy at the offsets of each form, agree between the two
+    images and with pack_np; the fragment image's pad rows hold byte 0 and stored value 0 (a zero: code 31)."""
+    from pgmi import _native as N
+    lib = N.lib()
+    rows, k = 40, 4096
+    w = _random_bits(77, (rows, k), 127, 30)
+    e_hi = P.e_hi_np(w)
+    assert P.fits_np(w)
+    n_r, n_f = lib.pgmi_pack13_bytes(rows, k), lib.pgmi_pack13_bytes_mf(rows, k)
+    assert n_r == P.image_bytes(rows, k) and n_f == P.image_bytes_mf(rows, k)
+    img_r, img_f = np.zeros(n_r, np.uint8), np.zeros(n_f, np.uint8)
+    assert lib.pgmi_pack13_encode(_p(w), rows, k, e_hi, _p(img_r)) == 0
+    assert lib.pgmi_pack13_encode_mf(_p(w), rows, k, e_hi, _p(img_f)) == 0
+    # row-major: segment row * (K / 2048) + s, lane l, chunk c, j holds k = 2048 s + 512 c + 8 l + j of that row
+    row, s, l, c, j = np.meshgrid(np.arange(rows), np.arange(k // P.SEG_WEIGHTS), np.arange(64), np.arange(4),
+                                  np.arange(8), indexing="ij")
+    kk = P.SEG_WEIGHTS * s + 512 * c + 8 * l + j
+    by_form = []
+    for img, (r_i, k_i) in ((img_r, (row, kk)), (img_f, P.frag_index_np(rows, k))):
+        sm, u = _read_back(img)
+        sm, u = sm.reshape(r_i.shape), u.reshape(r_i.shape)
+        real = r_i < rows
+        assert real.sum() == rows * k   # every weight exactly once (the index arrays are permutations of it)
+        sm_w, u_w = np.full((rows, k), 0xEE, np.uint8), np.full((rows, k), 0xEE, np.uint8)
+        sm_w[r_i[real], k_i[real]] = sm[real]
+        u_w[r_i[real], k_i[real]] = u[real]
+        by_form.append((sm_w, u_w))
+        assert not sm[~real].any() and not u[~real].any()   # pad rows (the fragment form's rows 40..47)
+    assert (~(P.frag_index_np(rows, k)[0] < rows)).sum() == 8 * k
+    (sm_r, u_r), (sm_f, u_f) = by_form
+    assert np.array_equal(sm_r, sm_f) and np.array_equal(u_r, u_f)
+    want_sm, want_code = P.pack_np(w, e_hi)
+    assert np.array_equal(sm_r, want_sm) and np.array_equal(u_r, 31 - want_code)
+
+
 def test_refusals_and_setters_without_a_device():
     from pgmi import _native as N
     from test_cpu_packed import _bare_ctx
