@@ -498,12 +498,26 @@ int pgmi_debug_gemm_tiles(int n_mt, int n_nt, int S, int BM, int BN, int K, int*
  * launch may still lower the split (workspace size, N % 4, empty K ranges).  No device needed. */
 int pgmi_debug_gemm_plan(int M, int N, int K, int dual, int* cfg, int* bm, int* bn, int* split);
 
-/* Tuning hook: force the prefill attention kernel (kernels_attn.hip): 0 = 16-row kernel with
- * LDS-resident scores, 7 = one pass with K/V loaded once and scores in registers (head_dim 72, <= 256 keys),
- * 8 = the same 16-row kernel with every K/V load issued up front (head_dim 256, <= 320 keys), RK = K/V-tiled two-pass kernel with R row groups and K key-split groups
- * per workgroup (41, 42, 21, 22; 44, 24 for head_dim 72); 9 = one pass with the keys split over workgroups
- * (online softmax, fp32 partials merged by a combine kernel), 91 / 92 / 94 = the same with 1 / 2 / 4 key
- * ranges; -1 restores the measured choice. */
+/* Test hook: what a prefill attention call of head_dim (72 or 256) over B x Lq queries, Lk keys, G query heads per
+ * KV head and n_kv KV heads launches (kernels_attn.hip attention_prefill_plan), under the pgmi_tune_attention
+ * override in force: kernel 0 = the short one-pass kernel, 1 = the one-pass key-split kernel; compute waves per
+ * workgroup (16 query rows each); key ranges and 32-key tiles per range (ranges > 1: the combine kernel follows).
+ * kernel 2 with the other three 0: an older kernel family is forced (0, RK or 81 below), which has no such plan.
+ * ragged != 0: the call carries per-row key counts; ws_floats: the fp32 scratch it hands over (0: none, no key
+ * split).  No device needed. */
+int pgmi_debug_attention_plan(int head_dim, int B, int Lq, int Lk, int G, int n_kv, int ragged, int64_t ws_floats,
+                              int* kernel, int* waves, int* ranges, int* tiles_per_range);
+
+/* Tuning hook: force the prefill attention kernel (kernels_attn.hip): 7 = one pass with K/V loaded once and
+ * scores in registers (head_dim 72, <= 256 keys); 9 = one pass with the keys split over workgroups (online
+ * softmax, fp32 partials merged by a combine kernel), 91 / 92 / 94 = the same with 1 / 2 / 4 key ranges;
+ * 82 / 81 = the same kernel with 2 / 1 compute waves per workgroup and one key range (head_dim 256); 0 = 16-row
+ * kernel with LDS-resident scores; RK = K/V-tiled two-pass kernel with R row groups and K key-split groups per
+ * workgroup (41, 42, 21, 22; 44, 24 for head_dim 72); -1 restores the measured choice.  Any other id is
+ * PGMI_E_ARG (8, the 16-row kernel with every load up front, was removed).  A forced 7 or 82 that a shape cannot
+ * take (the other head_dim, 7 past 256 keys) gets the measured choice for that shape -- it used to fall to the
+ * tiled kernel; 0, RK and 81 on a shape or head_dim they do not have still take the tiled kernel 42.  Ragged
+ * and prefix-LM calls ignore the override. */
 int pgmi_tune_attention(int variant);
 
 /* Nucleus sampling, inference.py:15-24 (_sample_top_p) with inference.py:65's

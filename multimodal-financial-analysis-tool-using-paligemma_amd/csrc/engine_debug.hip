@@ -253,6 +253,19 @@ int pgmi_debug_gemm_plan(int M, int N, int K, int dual, int* cfg, int* bm, int* 
     return 0;
 }
 
+int pgmi_debug_attention_plan(int head_dim, int B, int Lq, int Lk, int G, int n_kv, int ragged, int64_t ws_floats,
+                              int* kernel, int* waves, int* ranges, int* tiles_per_range) {
+    if ((head_dim != 72 && head_dim != 256) || B < 1 || Lq < 1 || Lk < 1 || G < 1 || n_kv < 1 || ws_floats < 0 ||
+        !kernel || !waves || !ranges || !tiles_per_range)
+        return fail(PGMI_E_ARG, "bad argument");
+    const AttnPlan p = attention_prefill_plan(head_dim, B, Lq, Lk, G, n_kv, ragged != 0, (long)ws_floats);
+    *kernel = p.kernel;
+    *waves = p.nw;
+    *ranges = p.ns;
+    *tiles_per_range = p.tps;
+    return 0;
+}
+
 int pgmi_tune_gemm(int cfg, int split) {
     if ((cfg >= 0 && !gemm_cfg_valid(cfg)) || split < 0 || split > 32) return fail(PGMI_E_ARG, "bad GEMM plan");
     gemm_force_plan(cfg, split);
@@ -268,7 +281,7 @@ int pgmi_tune_gemm_shape(int M, int N, int K, int dual, int cfg, int split) {
 }
 
 int pgmi_tune_attention(int variant) {
-    static const int ok[] = {-1, 0, 7, 8, 41, 42, 21, 22, 44, 24, 9, 91, 92, 94, 81, 82};
+    static const int ok[] = {-1, 0, 7, 41, 42, 21, 22, 44, 24, 9, 91, 92, 94, 81, 82};
     for (int v : ok)
         if (v == variant) {
             attention_force_variant(variant);

@@ -6,14 +6,22 @@
 //   GemmaAttention    modeling_gemma.py:262-277:   s = bf16(bf16(q.k) / 16) (+ zero mask, :269);
 //                                                  repeat_kv is never materialised: the G query heads of
 //                                                  a KV head are rows of one MFMA tile sharing its K/V.
-// The softmax is the exact two-pass one (global max and sum before any p is rounded), so p
-// rounds to bf16 exactly where the reference rounds it.
 //
-// Prefill (k_attn_full): one workgroup = 16 query rows x all keys; QK^T on MFMA straight from
-// global (both operands K-contiguous), scores in LDS (fp32), P in LDS (bf16), V staged
-// transposed in LDS 32 keys at a time for the PV MFMA.
-// Decode (Lq = 1): keys split over 64-key chunks across workgroups (flash-decoding), in three
-// short kernels: scores -> (global max/sum, P, partial P.V) -> fixed-order combine.
+// Prefill: the engine launches two kernels; attention_prefill_plan says which one a call takes and with what grid:
+//   k_attn_short (SigLIP at 224 px, one image: d 72, <= 256 keys): exact.  A workgroup sees every key, the
+//       row max and sum are global before any p is rounded, so p rounds to bf16 after normalisation, where
+//       the reference rounds it.
+//   k_attn_fs (+ k_attn_fs_combine; everything else, ragged and prefix-LM prefills included): one pass over
+//       the keys, which may be split over workgroups.  Online softmax with a deferred running max; p rounds to
+//       bf16 BEFORE normalisation (as exp(s - m), normalised in fp32 at the end) -- the flash-decoding
+//       deviation, DESIGN.md sec.5.
+//   Two older families, both exact, stay reachable through the tuning hook only (pgmi_tune_attention):
+//   k_attn_full (16 query rows x all keys per workgroup, the score matrix in LDS) and k_attn_fa (K/V-tiled, two
+//   passes).  A third, k_attn_full_pre (the 16-row kernel with every load up front), was removed; it was last
+//   present at commit 872ada3.
+// Decode (Lq = 1): flash-decoding over 64-key chunks; the body lives in attn_decode_body.h and the combine is
+// the prologue of gemv_o_attn.
+// The exact form for any shape is attention_exact (kernels_modules.hip, the drop-in modules).
 #include "attn_decode_body.h"
 #include "common.h"
 #include "launch.h"
@@ -25,7 +33,7 @@
 
 namespace pgmi {
 
-
+// tile counts of a head dim for k_attn_full
 template <int HD>
 struct HDInfo {
     static constexpr int KS = (HD + 31) / 32;   // 32-deep k-steps for QK^T
@@ -68,6 +76,10 @@ __device__ __forceinline__ void attn_out_rows(const AttnArgs& a, int b, int kvh,
     }
 }
 
+// ---------------------------------------------------------------- prefill, 16 rows (tuning hook only: variant 0)
+// One workgroup = 16 query rows x all keys; QK^T on MFMA straight from global (both operands K-contiguous),
+// scores in LDS (fp32), P in LDS (bf16), V staged in LDS 32 keys at a time for the PV MFMA (transposed reads).
+// The softmax is the exact two-pass one (global max and sum before any p is rounded).
 template <int HD>
 __global__ void __launch_bounds__(256) k_attn_full(AttnArgs a) {
     using I = HDInfo<HD>;
@@ -211,173 +223,7 @@ __global__ void __launch_bounds__(256) k_attn_full(AttnArgs a) {
     }
 }
 
-// ---------------------------------------------------------------- prefill, 16 rows, loads up front
-// k_attn_full for short key ranges (Gemma at 224 px: 288 keys x d 256, MQA): the same three phases,
-// but every global load of the workgroup is issued before the first one is consumed -- each wave's
-// K fragments for all its 16-key tiles, then the V rows of every 32-key chunk (VGPR-resident until
-// their chunk is staged) -- so the kernel pays one L2 round trip instead of one per K tile and per
-// V chunk.  Keys <= 16 * 4 * MAXT and <= 32 * MAXC.  Scores are kept in LDS as bf16 (they are
-// bf16-rounded values, modeling_gemma.py:266) and P overwrites them row by row.
-template <int HD, int MAXT, int MAXC>
-__global__ void __launch_bounds__(256) k_attn_full_pre(AttnArgs a) {
-    using I = HDInfo<HD>;
-    constexpr int HDP = I::CT * 16;
-    constexpr int VS = HDP + 16;
-    constexpr int CHK = 32;
-    constexpr int VPT = (CHK * I::CH + 255) / 256;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int LkP = (a.Lk + 31) & ~31;
-    uint16_t* S = reinterpret_cast<uint16_t*>(smem_raw);  // [16][LkP] bf16 P
-    uint16_t* Vl = S + 16 * LkP;                          // [2][CHK][VS], then [2][4][16] fp32 row stats
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.z, kvh = blockIdx.y;
-    const int row0 = blockIdx.x * 16;
-    const int nrows = a.Lq * a.G;
-    const int qi = row0 + (lane & 15);
-    const bool qvalid = qi < nrows;
-    const int qpos = qvalid ? qi / a.G : 0, qhead = kvh * a.G + (qvalid ? qi % a.G : 0);
-    const uint16_t* qrow = a.q + b * a.q_b_stride + (long)qpos * a.q_row_stride + qhead * a.q_head_stride;
-    const uint16_t* kbase = a.k + b * a.k_b_stride + kvh * a.k_head_stride;
-    const uint16_t* vbase = a.v + b * a.v_b_stride + kvh * a.v_head_stride;
-    const int ntile = LkP / 16, nch = LkP / CHK;
-
-    short8 qf[I::KS];
-#pragma unroll
-    for (int kk = 0; kk < I::KS; ++kk) qf[kk] = load_frag<HD>(qrow, qvalid, kk, lane);
-    // K fragments of this wave's tiles t = wave + 4j, then every V chunk: all in flight together
-    short8 kf[MAXT][I::KS];
-#pragma unroll
-    for (int j = 0; j < MAXT; ++j) {
-        const int key = (wave + 4 * j) * 16 + (lane & 15);
-        const bool ok = key < a.Lk;
-        const uint16_t* krow = kbase + (long)(ok ? key : 0) * a.k_row_stride;
-#pragma unroll
-        for (int kk = 0; kk < I::KS; ++kk) kf[j][kk] = load_frag<HD>(krow, ok, kk, lane);
-    }
-    uint4 vr[MAXC][VPT];
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            int e = tid + 256 * i;
-            if (CHK * I::CH % 256 != 0 && e >= CHK * I::CH) e = 0;  // tail lanes (HD 72): re-read piece 0, not stored
-            const int key = c * CHK + e / I::CH, ch = e % I::CH;
-            vr[c][i] = ldg16(vbase + (long)(key < a.Lk ? key : a.Lk - 1) * a.v_row_stride + ch * 8);  // p = 0 past Lk
-        }
-
-    // ---- phase 1: s = bf16(bf16(Q K^T) * scale), kept in registers: lane (g, li) holds rows 4g + r
-    // of keys 16 t + li for this wave's tiles t = wave + 4 j
-    const int g = lane >> 4, li = lane & 15;
-    float sc[MAXT][4];
-#pragma unroll
-    for (int j = 0; j < MAXT; ++j) {
-        const int t = wave + 4 * j;
-        const int key = t * 16 + li;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < I::KS; ++kk) acc = mfma16(qf[kk], kf[j][kk], acc);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[j][r] = (t < ntile && key < a.Lk) ? rbf(rbf(acc[r]) * a.scale) : -INFINITY;
-    }
-    // ---- phase 2: exact softmax per row: max and sum of exp over the row's keys (lane, then the 16
-    // lanes of a row group, then the 4 waves in a fixed order), p = bf16(exp(s - max) / sum) -> LDS
-    float* red = reinterpret_cast<float*>(Vl + 2 * CHK * VS);  // [2][4 waves][16 rows]
-    float mx[4], sm[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        mx[r] = sc[0][r];
-#pragma unroll
-        for (int j = 1; j < MAXT; ++j) mx[r] = fmaxf(mx[r], sc[j][r]);
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], o, 64));
-    if (li == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[wave * 16 + 4 * g + r] = mx[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = 4 * g + r;
-        mx[r] = fmaxf(fmaxf(red[row], red[16 + row]), fmaxf(red[32 + row], red[48 + row]));
-        sm[r] = 0.f;
-#pragma unroll
-        for (int j = 0; j < MAXT; ++j) {
-            sc[j][r] = sc[j][r] == -INFINITY ? 0.f : expf(sc[j][r] - mx[r]);
-            sm[r] += sc[j][r];
-        }
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sm[r] += __shfl_xor(sm[r], o, 64);
-    if (li == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[64 + wave * 16 + 4 * g + r] = sm[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = 4 * g + r;
-        const float L = ((red[64 + row] + red[80 + row]) + red[96 + row]) + red[112 + row];
-#pragma unroll
-        for (int j = 0; j < MAXT; ++j) {
-            const int key = (wave + 4 * j) * 16 + li;
-            if (key < LkP) S[row * LkP + key] = key < a.Lk ? f2bf(sc[j][r] / L) : 0;
-        }
-    }
-    // ---- phase 3: O = bf16(P V), V chunks staged from registers into two LDS buffers
-    f32x4 oacc[(I::CT + 3) / 4];
-#pragma unroll
-    for (int c = 0; c < (I::CT + 3) / 4; ++c) oacc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        if (c < nch) {  // uniform: no early exit, so the register arrays stay statically indexed
-        const int buf = c & 1;
-#pragma unroll
-        for (int i = 0; i < VPT; ++i) {
-            const int e = tid + 256 * i;
-            if (e < CHK * I::CH)
-                *reinterpret_cast<uint4*>(Vl + (buf * CHK + e / I::CH) * VS + (e % I::CH) * 8) = vr[c][i];
-        }
-        if constexpr (HDP != I::CH * 8) {
-            for (int e = tid; e < CHK; e += 256)
-                *reinterpret_cast<uint4*>(Vl + (buf * CHK + e) * VS + I::CH * 8) = make_uint4(0, 0, 0, 0);
-        }
-        __syncthreads();  // V chunk (and, at c == 0, all of P) visible; buffer buf^1 free
-        const short8 pa = *reinterpret_cast<const short8*>(S + (lane & 15) * LkP + c * CHK + 8 * g);
-#pragma unroll
-        for (int cc = 0; cc < (I::CT + 3) / 4; ++cc) {
-            const int ct = wave + 4 * cc;
-            if (ct < I::CT) {
-                const uint16_t* vp = Vl + (buf * CHK + 8 * g + (li >> 2)) * VS + ct * 16 + 4 * (li & 3);
-                const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(vp));
-                const s4v hi =
-                    __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(vp + 4 * VS));
-                const short8 vb = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                oacc[cc] = mfma16(pa, vb, oacc[cc]);
-            }
-        }
-        }
-    }
-    uint16_t* orow[4];
-    attn_out_rows(a, b, kvh, row0 + (lane >> 4) * 4, nrows, orow);
-#pragma unroll
-    for (int c = 0; c < (I::CT + 3) / 4; ++c) {
-        const int ct = wave + 4 * c;
-        if (ct >= I::CT) continue;
-        const int d = ct * 16 + (lane & 15);
-        if (d >= HD) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (orow[r]) orow[r][d] = f2bf(oacc[c][r]);
-    }
-}
-
-// ---------------------------------------------------------------- prefill, K/V-tiled (two pass)
+// ---------------------------------------------------------------- prefill, K/V-tiled, two pass (tuning hook only)
 // One workgroup = RG x 16 query rows (RG waves, one 16-row group each) x all keys, K/V streamed
 // through LDS in 32-key tiles that every wave of the workgroup shares (the 16-row kernel above
 // re-read the whole K and V from L2 for every 16 rows).  KSPL key-split groups of RG waves
@@ -652,8 +498,8 @@ __global__ void __launch_bounds__(64 * RG * KSPL) k_attn_fa(AttnArgs a) {
 // are bank-conflict free).  Scores stay in registers (no second pass over the keys); the exact
 // softmax's row max and sum meet across the 4 waves in LDS in a fixed order; each wave multiplies its
 // own keys' p = bf16(exp(s - M) / L) by V, and the 4 partial O tiles are summed in a fixed order and
-// rounded once -- the rounding points of k_attn_fa (s = bf16(bf16(k.q) * scale), p rounded after
-// normalisation, O rounded once), one global round trip instead of one per 32-key tile and pass.
+// rounded once.  Rounding points, the reference's: s = bf16(bf16(k.q) * scale), p rounded to bf16 after
+// normalisation, O rounded once.  One global round trip, where k_attn_fa takes one per 32-key tile and pass.
 template <int HD, int MAXT>
 __global__ void __launch_bounds__(256) k_attn_short(AttnArgs a) {
     using I = FAInfo<HD>;
@@ -1139,67 +985,134 @@ __global__ void __launch_bounds__(256) k_attn_fs_combine(AttnArgs a, int ns) {
 // key ranges for k_attn_fs.  A workgroup takes the whole LDS (one per CU), so a grid past 256
 // workgroups runs in two rounds: split the keys (2, 4, ...) only while the grid stays within one
 // round and every range keeps >= 16 tiles (shorter ranges lose more to the combine than they gain);
-// scratch for the partials or the split is dropped
-static int fs_splits(const AttnArgs& a, int HD, int QB, int want) {
-    const int nrows = a.Lq * a.G, nt = (a.Lk + 31) / 32;
-    const long blocks = (long)(nrows + QB - 1) / QB * a.n_kv * a.B;
+// scratch for the partials (ws_floats) or the split is dropped.  QB: query rows per workgroup; want > 0: that
+// many ranges instead of the rule's
+static int fs_splits(int HD, int QB, int want, int B, int nrows, int Lk, int n_kv, long ws_floats) {
+    const int nt = (Lk + 31) / 32;
+    const long blocks = (long)(nrows + QB - 1) / QB * n_kv * B;
     int ns = 1;
     if (want > 0) ns = want;
     else
         while (blocks * ns * 2 <= 256 && nt / (ns * 2) >= 16) ns *= 2;
     if (ns > nt) ns = nt;
-    while (ns > 1 && (!a.ws || (long)a.B * a.n_kv * ns * nrows * (HD + 2) > a.ws_floats)) ns >>= 1;
+    while (ns > 1 && (long)B * n_kv * ns * nrows * (HD + 2) > ws_floats) ns >>= 1;
     return ns < 1 ? 1 : ns;
 }
 
+// false: the runtime refused the kernel's LDS size; the error is recorded and nothing was launched
 template <int HD, int NW, int LW, int ST, bool P2, bool KL = false, bool CA = false>
-static void launch_fs_t(hipStream_t s, const FsArgs<CA>& a, int ns, int tps, dim3 grid) {
+static bool launch_fs_t(hipStream_t s, const FsArgs<CA>& a, int ns, int tps, dim3 grid) {
     constexpr size_t lds = (size_t)ST * FSInfo<HD>::SLOTB;
     static_assert(lds <= 160 * 1024, "LDS");
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fs<HD, NW, LW, ST, P2, KL, CA>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fs<HD, NW, LW, ST, P2, KL, CA>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            launch_error_set(e, "k_attn_fs: dynamic LDS size");
+            return false;
+        }
         attr = true;
     }
     hipLaunchKernelGGL((k_attn_fs<HD, NW, LW, ST, P2, KL, CA>), grid, dim3(64 * (NW + LW)), lds, s, a, ns, tps);
+    return true;
 }
 
-// the key ranges and the tiles per range of a launch: no empty range
-static int fs_plan(const AttnArgs& a, int HD, int QB, int want, int* tps) {
-    const int nt = (a.Lk + 31) / 32;
-    const int ns = fs_splits(a, HD, QB, want);
-    *tps = (nt + ns - 1) / ns;
-    return (nt + *tps - 1) / *tps;
-}
-
-template <int HD, int NWQ = 0, bool CA = false>
-static void launch_fs(hipStream_t s, const FsArgs<CA>& a, int want_ns) {
+// k_attn_fs (and its combine) as planned: NW compute waves, p.ns key ranges of p.tps tiles
+template <int HD, int NW, bool CA = false>
+static void launch_fs(hipStream_t s, const FsArgs<CA>& a, const AttnPlan& p) {
     // head dim 256: 4 compute waves (their registers fit 2 waves per SIMD with the loaders, not 3) and a
-    // 5-slot ring (160 KiB); head dim 72: 8 compute waves, 8 slots.  NWQ > 0: that many compute waves (fewer
-    // query rows per workgroup, more workgroups over the same keys: probe variants 81 / 82)
-    constexpr int NW = NWQ > 0 ? NWQ : HD == 256 ? 4 : 8, LW = 4, ST = HD == 256 ? 5 : 8;
-    const int nrows = a.Lq * a.G;
-    int tps = 0;
-    const int ns = fs_plan(a, HD, NW * 16, want_ns, &tps);
+    // 5-slot ring (160 KiB); head dim 72: 8 compute waves, 8 slots.  2 compute waves (head dim 256): fewer
+    // query rows per workgroup, more workgroups over the same keys (variant 82)
+    constexpr int LW = 4, ST = HD == 256 ? 5 : 8;
+    const int nrows = a.Lq * a.G, ns = p.ns, tps = p.tps;
     dim3 grid((nrows + NW * 16 - 1) / (NW * 16), a.n_kv * ns, a.B);
     int e2 = 0;
     const bool p2 = std::frexp(a.scale, &e2) == 0.5f;
+    bool ok = false;
     if constexpr (CA) {  // prefix-LM prefill: per-query key limits over the rows' key counts
-        if (p2) launch_fs_t<HD, NW, LW, ST, true, true, true>(s, a, ns, tps, grid);
-        else launch_fs_t<HD, NW, LW, ST, false, true, true>(s, a, ns, tps, grid);
-    } else if (a.klen) {  // ragged prefill (head dim 256, the default compute-wave count): per-row key counts
-        if constexpr (HD == 256 && NWQ == 0) {
-            if (p2) launch_fs_t<HD, NW, LW, ST, true, true>(s, a, ns, tps, grid);
-            else launch_fs_t<HD, NW, LW, ST, false, true>(s, a, ns, tps, grid);
-        }
-    } else if (p2) launch_fs_t<HD, NW, LW, ST, true>(s, a, ns, tps, grid);
-    else launch_fs_t<HD, NW, LW, ST, false>(s, a, ns, tps, grid);
-    if (ns > 1) {
+        ok = p2 ? launch_fs_t<HD, NW, LW, ST, true, true, true>(s, a, ns, tps, grid)
+                : launch_fs_t<HD, NW, LW, ST, false, true, true>(s, a, ns, tps, grid);
+    } else if (a.klen) {  // ragged prefill: per-row key counts.  Head dim 256 with 4 compute waves is what the plan
+                          // gives such a call (attention_prefill refuses the other head dim), so no other instance
+        if constexpr (HD == 256 && NW == 4)
+            ok = p2 ? launch_fs_t<HD, NW, LW, ST, true, true>(s, a, ns, tps, grid)
+                    : launch_fs_t<HD, NW, LW, ST, false, true>(s, a, ns, tps, grid);
+    } else {
+        ok = p2 ? launch_fs_t<HD, NW, LW, ST, true>(s, a, ns, tps, grid)
+                : launch_fs_t<HD, NW, LW, ST, false>(s, a, ns, tps, grid);
+    }
+    if (ok && ns > 1) {
         const long n8 = (long)a.B * a.n_kv * nrows * (HD / 8);
         hipLaunchKernelGGL(k_attn_fs_combine<HD>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, a, ns);
     }
 }
+
+// attention variant override (tuning hook pgmi_tune_attention): 7 = the short one-pass kernel (HD 72, <= 256
+// keys), 9 = the one-pass key-split kernel with the ranges of fs_splits, 91 / 92 / 94 = with 1 / 2 / 4 ranges,
+// 82 = with 2 compute waves per workgroup and one range (HD 256); -1 = the measured choice.  The older families,
+// which the measured choice never takes: 0 = the 16-row kernel, RK = the tiled kernel with RG = R, KSPL = K
+// (41, 42, 21, 22; 44 and 24 for HD 72), 81 = the key-split kernel with 1 compute wave (HD 256).
+// Every variant is forced and checked against the oracle by tests/test_gpu_ops.py.
+static int g_attn_force = -1;
+
+void attention_force_variant(int v) { g_attn_force = v; }
+
+long tune_epoch(int bump) {
+    static std::atomic<long> n{0};
+    return n += bump;
+}
+
+static bool older_variant(int v) {
+    return v == 0 || v == 41 || v == 42 || v == 21 || v == 22 || v == 44 || v == 24 || v == 81;
+}
+
+// the plan under override v: a function of its arguments alone
+static AttnPlan plan_under(int v, int head_dim, int B, int Lq, int Lk, int G, int n_kv, bool ragged, long ws_floats) {
+    const int nrows = Lq * G, nt = (Lk + 31) / 32;
+    const long rows = (long)nrows * n_kv * B;
+    if (ragged && head_dim == 256) v = 9;  // per-row key counts: the key-split kernel's ragged form, whatever is forced
+    else if (older_variant(v)) return {2, 0, 0, 0};  // launch_older
+    else {
+        // forced on a shape it does not cover: the measured choice
+        if ((v == 7 && (head_dim != 72 || Lk > 256)) || (v == 82 && head_dim != 256)) v = -1;
+        if (v < 0) {
+            // measured on MI355X (tools/probes/attn_bench.py, graph-replayed, round 3), us per call, against the
+            // 16-row and the K/V-tiled two-pass kernels:
+            //   Gemma 224 12.2 (16-row with its loads up front, since removed: 15.1) | Gemma 448 31.7 (tiled 52.5) |
+            //   SigLIP 448 24.4 (31.8);
+            //   SigLIP 224 stays on k_attn_short at one image (6.7 against 10.6); at 8 images
+            //   (tools/probes/plan_sweep.py --batch 8, whole tower) k_attn_fs: tower 4204 -> 3835 us
+            // round 6: Gemma at one 224 px image (288 queries x 8 heads, 288 keys: no key split, 36 workgroups of
+            // 4 compute waves) takes 2 compute waves per workgroup, 72 workgroups over the same keys: in situ LM
+            // prefill 2,408.7 -> 2,394.0 us (variant 82; 1 compute wave, 81: 2,396.0)
+            if (head_dim == 72 && Lk <= 256 && rows <= 4096) v = 7;
+            else if (head_dim == 256 && nt < 16 && (rows + 31) / 32 <= 256) v = 82;
+            else v = 9;
+        }
+    }
+    if (v == 7) return {0, 4, 1, nt};
+    const int nw = v == 82 ? 2 : head_dim == 256 ? 4 : 8;
+    const int want = v == 82 ? 1 : v == 9 ? 0 : v - 90;
+    const int ns = fs_splits(head_dim, nw * 16, want, B, nrows, Lk, n_kv, ws_floats);
+    const int tps = (nt + ns - 1) / ns;
+    return {1, nw, (nt + tps - 1) / tps, tps};  // no empty range
+}
+
+AttnPlan attention_prefill_plan(int head_dim, int B, int Lq, int Lk, int G, int n_kv, bool ragged, long ws_floats) {
+    return plan_under(g_attn_force, head_dim, B, Lq, Lk, G, n_kv, ragged, ws_floats);
+}
+
+static AttnPlan plan_of(int v, int head_dim, const AttnArgs& a, bool ragged) {
+    return plan_under(v, head_dim, a.B, a.Lq, a.Lk, a.G, a.n_kv, ragged, a.ws ? a.ws_floats : 0);
+}
+
+// a prefix-LM call takes the plan of a ragged one (klen set): 4 compute waves, the ranges of fs_splits
+void attention_prefill_prefix(hipStream_t s, const AttnPrefixArgs& a) {
+    launch_fs<256, 4, true>(s, a, plan_of(g_attn_force, 256, a, true));
+}
+
+int attention_prefill_splits(const AttnArgs& a) { return plan_of(g_attn_force, 256, a, true).ns; }
 
 template <int HD, int RG, int KSPL>
 static void launch_fa(hipStream_t s, const AttnArgs& a) {
@@ -1216,20 +1129,6 @@ static void launch_fa(hipStream_t s, const AttnArgs& a) {
     hipLaunchKernelGGL((k_attn_fa<HD, RG, KSPL, 1>), grid, dim3(64 * RG * KSPL), lds, s, a);
 }
 
-// attention variant override (tuning hook pgmi_tune_attention): 0 = the 16-row kernel, 7 = the
-// one-pass short-range kernel (HD 72, <= 256 keys), 8 = the
-// 16-row kernel with every load up front (HD 256, <= 320 keys), RK = the tiled kernel with RG = R,
-// KSPL = K (41, 42, 21, 22; 44 and 24 for HD 72); -1 = the measured choice in attention_prefill.
-// Every variant is forced and checked against the oracle by tests/test_gpu_ops.py.
-static int g_attn_force = -1;
-
-void attention_force_variant(int v) { g_attn_force = v; }
-
-long tune_epoch(int bump) {
-    static std::atomic<long> n{0};
-    return n += bump;
-}
-
 template <int HD>
 static void launch_fa_variant(hipStream_t s, const AttnArgs& a, int rk) {
     switch (rk) {
@@ -1243,96 +1142,51 @@ static void launch_fa_variant(hipStream_t s, const AttnArgs& a, int rk) {
     launch_fa<HD, 4, 2>(s, a);  // 42
 }
 
-static size_t attn_full_lds(int head_dim, int Lk) {
-    const int LkP = (Lk + 31) & ~31;
+// the 16-row kernel keeps a workgroup's whole score matrix in LDS: the keys it can take
+static int attn_full_max_keys(int head_dim) {
     const int hdp = (head_dim + 15) / 16 * 16;
-    return (size_t)16 * LkP * 4 + (size_t)16 * LkP * 2 + (size_t)2 * 32 * (hdp + 16) * 2;
+    return (int)((160 * 1024 - (size_t)2 * 32 * (hdp + 16) * 2) / (16 * 6)) & ~31;
 }
 
-void attention_prefill_prefix(hipStream_t s, const AttnPrefixArgs& a) { launch_fs<256, 0, true>(s, a, 0); }
+template <int HD>
+static void launch_full(hipStream_t s, const AttnArgs& a) {
+    const int LkP = (a.Lk + 31) & ~31;
+    const size_t lds = (size_t)16 * LkP * 4 + (size_t)16 * LkP * 2 + (size_t)2 * 32 * ((HD + 15) / 16 * 16 + 16) * 2;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_full<HD>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr = true;
+    }
+    dim3 grid((a.Lq * a.G + 15) / 16, a.n_kv, a.B);
+    hipLaunchKernelGGL(k_attn_full<HD>, grid, dim3(256), lds, s, a);
+}
 
-int attention_prefill_splits(const AttnArgs& a) {
-    int tps = 0;
-    return fs_plan(a, 256, 4 * 16, 0, &tps);
+// a forced variant of the older families (plan kernel 2); one a shape or head dim does not have: the tiled kernel, 42
+static void launch_older(hipStream_t s, int head_dim, const AttnArgs& a, int v) {
+    const int nt = (a.Lk + 31) / 32;
+    if (v == 81 && head_dim == 256) launch_fs<256, 1>(s, a, AttnPlan{1, 1, 1, nt});
+    else if (v == 0 && a.Lk <= attn_full_max_keys(head_dim)) {
+        if (head_dim == 256) launch_full<256>(s, a);
+        else launch_full<72>(s, a);
+    } else if (head_dim == 256) launch_fa_variant<256>(s, a, v);
+    else launch_fa_variant<72>(s, a, v);
 }
 
 void attention_prefill(hipStream_t s, int head_dim, const AttnArgs& a) {
-    if (a.klen && head_dim == 256) {  // ragged: always the one-pass key-split kernel (it honours klen)
-        launch_fs<256>(s, a, 0);
+    if (a.klen && head_dim != 256) {
+        launch_error_set(hipErrorInvalidValue, "attention_prefill: per-row key counts need head dim 256");
         return;
     }
-    int v = g_attn_force;
-    if (v < 0) {
-        // measured on MI355X (tools/probes/attn_bench.py, round 1), us per call:
-        //   SigLIP 224 (256 rows x 16 heads):  16-row 16.4 | RG2xKSPL4 10.8 | RG4xKSPL2 13.5
-        //   SigLIP 448 (1024 x 16):            16-row 153.5 | RG4xKSPL4 32.4 | RG4xKSPL2 36.0
-        //   Gemma 224 (288 x 8 heads, MQA):    16-row 21.9 | RG4xKSPL2 26.1 | RG2xKSPL2 26.4
-        //   Gemma 448 (1056 x 8):              16-row 159.5 | RG4xKSPL2 61.3 | RG2xKSPL2 122.7
-        // round 3 (same probe, graph-replayed): the one-pass key-split kernel k_attn_fs (variant 9)
-        //   Gemma 224 12.2 (full_pre 15.1) | Gemma 448 31.7 (tiled RG4xKSPL2 52.5) | SigLIP 448 24.4 (31.8);
-        //   SigLIP 224 stays on k_attn_short at one image (6.7 against 10.6); at 8 images
-        //   (tools/probes/plan_sweep.py --batch 8, whole tower) k_attn_fs: tower 4204 -> 3835 us
-        const long rows = (long)a.Lq * a.G * a.n_kv * a.B;
-        v = head_dim == 256 ? 9 : (a.Lk <= 256 && rows <= 4096) ? 7 : 9;
-        // round 6: Gemma at one 224 px image (288 queries x 8 heads, 288 keys: no key split, 36 workgroups of
-        // 4 compute waves) takes 2 compute waves per workgroup, 72 workgroups over the same keys: in situ LM
-        // prefill 2,408.7 -> 2,394.0 us (gpurun_out r6g, variant 82; 1 wave, 81: 2,396.0)
-        if (head_dim == 256 && (a.Lk + 31) / 32 < 16 && (rows + 31) / 32 <= 256) v = 82;
-    }
-    if ((v == 81 || v == 82) && head_dim == 256) {  // one pass, 1 / 2 compute waves per workgroup, one key range
-        if (v == 81) launch_fs<256, 1>(s, a, 1);
-        else launch_fs<256, 2>(s, a, 1);
-        return;
-    }
-    if (v == 9 || v == 91 || v == 92 || v == 94) {  // one pass, keys split over workgroups (auto / 1 / 2 / 4 ranges)
-        const int want = v == 9 ? 0 : v - 90;
-        if (head_dim == 256) launch_fs<256>(s, a, want);
-        else launch_fs<72>(s, a, want);
-        return;
-    }
-    if (v == 7 && head_dim == 72 && a.Lk <= 256) {
+    const int v = g_attn_force;  // read once: the plan and the launch see the same override
+    const AttnPlan p = plan_of(v, head_dim, a, a.klen != nullptr);
+    if (p.kernel == 2) launch_older(s, head_dim, a, v);
+    else if (p.kernel == 0) {
         dim3 grid((a.Lq * a.G + 15) / 16, a.n_kv, a.B);
         hipLaunchKernelGGL((k_attn_short<72, 4>), grid, dim3(256), 0, s, a);
-        return;
-    }
-    if (v == 7) v = head_dim == 256 ? 42 : 24;  // forced on a shape it does not cover: the tiled kernel
-    if (v == 8 && head_dim == 256 && a.Lk <= 320) {
-        // 16 query rows per workgroup, every K/V load issued up front (Lk <= 320)
-        const size_t lds = (size_t)16 * ((a.Lk + 31) & ~31) * 2 + (size_t)2 * 32 * (256 + 16) * 2 + 2 * 4 * 16 * 4;
-        dim3 grid((a.Lq * a.G + 15) / 16, a.n_kv, a.B);
-        hipLaunchKernelGGL((k_attn_full_pre<256, 5, 10>), grid, dim3(256), lds, s, a);
-        return;
-    }
-    if (v == 8) v = 0;
-    if (v != 0 || a.Lk > attention_prefill_max_keys(head_dim)) {
-        if (head_dim == 256) launch_fa_variant<256>(s, a, v);
-        else launch_fa_variant<72>(s, a, v);
-        return;
-    }
-    const size_t lds = attn_full_lds(head_dim, a.Lk);
-    dim3 grid((a.Lq * a.G + 15) / 16, a.n_kv, a.B);
-    if (head_dim == 256) {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_full<256>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr = true;
-        }
-        hipLaunchKernelGGL(k_attn_full<256>, grid, dim3(256), lds, s, a);
-    } else {
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_full<72>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr = true;
-        }
-        hipLaunchKernelGGL(k_attn_full<72>, grid, dim3(256), lds, s, a);
-    }
-}
-
-int attention_prefill_max_keys(int head_dim) {
-    const int hdp = (head_dim + 15) / 16 * 16;
-    return (int)((160 * 1024 - (size_t)2 * 32 * (hdp + 16) * 2) / (16 * 6)) & ~31;
+    } else if (head_dim == 72) launch_fs<72, 8>(s, a, p);
+    else if (p.nw == 2) launch_fs<256, 2>(s, a, p);
+    else launch_fs<256, 4>(s, a, p);
 }
 
 // ================================================================ decode (Lq = 1)

@@ -208,6 +208,15 @@ struct AttnArgs {
     const int* klen;
 };
 void attention_prefill(hipStream_t s, int head_dim, const AttnArgs& a);
+// What a prefill attention call of this shape launches, under the tuning override in force: kernel 0 = the short
+// one-pass kernel (head dim 72, <= 256 keys), 1 = the one-pass key-split kernel; nw = compute waves per workgroup
+// (16 query rows each); ns key ranges of tps 32-key tiles (ns > 1: the combine kernel follows).  kernel 2 (the
+// other fields 0): a forced variant of the older families, which only the tuning hook reaches.  ragged: the call
+// sets klen; ws_floats: the fp32 scratch it hands over (0: none).  A pure host function: no device needed.
+struct AttnPlan {
+    int kernel, nw, ns, tps;
+};
+AttnPlan attention_prefill_plan(int head_dim, int B, int Lq, int Lk, int G, int n_kv, bool ragged, long ws_floats);
 // prefix-LM prefill (head dim 256, klen set): query position j of batch row b attends keys [0, min(klen[b],
 // kv_start + max(pfx[b], j + 1))) -- the kv_start cached rows and the row's prefix (pfx, a device array indexed like
 // klen) from everywhere, the rest causally.  The argument of the one-pass key-split kernel's prefix instances alone:
@@ -227,7 +236,6 @@ void attention_decode(hipStream_t s, const AttnArgs& a, const StepState* st, int
 constexpr int kAttnChunk = 64;
 constexpr int kAttnPartStride = 16 * 256 + 32;  // floats per (b, kv head, chunk) record
 size_t attention_decode_part_floats(int B, int n_kv, int max_chunks);
-int attention_prefill_max_keys(int head_dim);
 void attention_force_variant(int v);  // tuning hook (kernels_attn.hip); -1 = measured choice
 // the process-wide count of tuning calls (pgmi_tune_gemm, pgmi_tune_gemm_shape, pgmi_tune_attention), an element
 // of every prefill graph key (engine_graph.h): bump = 1 counts one more call; returns the count

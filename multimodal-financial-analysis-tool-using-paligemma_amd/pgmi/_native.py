@@ -106,6 +106,7 @@ SIGNATURES = {
     "pgmi_prefill_kernel": (i32, [vp, i32, i32, i32, vp]),
     "pgmi_debug_gemm_tiles": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "pgmi_debug_gemm_plan": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
+    "pgmi_debug_attention_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp]),
     "pgmi_prefill_probe": (i32, [vp, i32]),
     "pgmi_prefill_probe_times": (i32, [vp, ctypes.POINTER(f32), i32]),
     "pgmi_preprocess": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),

@@ -142,6 +142,72 @@ def test_gemm_plans_are_pinned():
     assert _gemm_plan(lib, 288, 2048, 2048, 0) == (34, 128, 128, 4)
 
 
+WS = 1 << 28
+# (forced variant, (head_dim, B, Lq, Lk, G, n_kv), ragged, ws_floats) -> (kernel, waves, ranges, tiles per range):
+# what the dispatch of commit 872ada3 (a cascade of if-blocks inside attention_prefill) gave these calls,
+# transliterated from it line by line; the rows where a forced 7 or 82 does not cover the shape give the measured
+# choice (there they gave the tiled kernel)
+ATTN_PLANS = [
+    (-1, (72, 1, 256, 256, 1, 16), 0, WS, (0, 4, 1, 8)),       # SigLIP 224, one image: short
+    (-1, (72, 2, 256, 256, 1, 16), 0, WS, (1, 8, 1, 8)),       # rows > 4096: key-split kernel
+    (-1, (72, 8, 256, 256, 1, 16), 0, WS, (1, 8, 1, 8)),       # 8 images
+    (-1, (72, 1, 16, 257, 1, 16), 0, WS, (1, 8, 1, 9)),        # Lk boundary 256 / 257
+    (-1, (72, 1, 1024, 1024, 1, 16), 0, WS, (1, 8, 2, 16)),    # SigLIP 448: two ranges
+    (-1, (72, 1, 1024, 1024, 1, 16), 0, 0, (1, 8, 1, 32)),     # no scratch: split dropped
+    (-1, (256, 1, 288, 288, 8, 1), 0, WS, (1, 2, 1, 9)),       # Gemma 224: variant 82
+    (-1, (256, 3, 288, 288, 8, 1), 0, WS, (1, 2, 1, 9)),       # 82 up to 256 row blocks ...
+    (-1, (256, 4, 288, 288, 8, 1), 0, WS, (1, 4, 1, 9)),       # ... and not past them
+    (-1, (256, 1, 16, 480, 8, 1), 0, WS, (1, 2, 1, 15)),       # 15 tiles: 82
+    (-1, (256, 1, 16, 481, 8, 1), 0, WS, (1, 4, 1, 16)),       # 16 tiles: 9
+    (-1, (256, 1, 1056, 1056, 8, 1), 0, WS, (1, 4, 1, 33)),    # Gemma 448
+    (-1, (256, 1, 1, 2000, 8, 1), 0, WS, (1, 4, 2, 32)),       # one query row, long cache
+    (-1, (256, 2, 300, 1000, 8, 1), 0, WS, (1, 4, 2, 16)),
+    (-1, (256, 1, 40, 2100, 8, 1), 0, WS, (1, 4, 4, 17)),
+    (-1, (256, 1, 288, 288, 8, 1), 1, WS, (1, 4, 1, 9)),       # ragged never takes 82
+    (94, (256, 2, 33, 70, 8, 1), 0, WS, (1, 4, 3, 1)),         # more ranges wanted than tiles
+    (92, (256, 1, 288, 288, 8, 1), 0, WS, (1, 4, 2, 5)),
+    (91, (72, 1, 1024, 1024, 1, 16), 0, WS, (1, 8, 1, 32)),
+    (9, (256, 1, 288, 288, 8, 1), 0, WS, (1, 4, 1, 9)),
+    (82, (256, 1, 1056, 1056, 8, 1), 0, WS, (1, 2, 1, 33)),
+    (7, (72, 8, 256, 256, 1, 16), 0, WS, (0, 4, 1, 8)),        # forced onto a covered shape
+    (7, (256, 1, 288, 288, 8, 1), 0, WS, (1, 2, 1, 9)),        # uncovered: measured choice
+    (7, (72, 1, 1024, 1024, 1, 16), 0, WS, (1, 8, 2, 16)),     # uncovered (Lk > 256)
+    (82, (72, 1, 256, 256, 1, 16), 0, WS, (0, 4, 1, 8)),       # uncovered: measured choice
+    (42, (256, 1, 288, 288, 8, 1), 0, WS, (2, 0, 0, 0)),       # an older family forced: no plan of this kind
+    (0, (72, 1, 256, 256, 1, 16), 0, WS, (2, 0, 0, 0)),
+    (81, (256, 1, 288, 288, 8, 1), 1, WS, (1, 4, 1, 9)),       # ... which a ragged call ignores as well
+]
+
+
+def test_attention_plans_are_pinned():
+    """pgmi_debug_attention_plan (kernels_attn.hip attention_prefill_plan): the kernel, its compute waves, the key
+    ranges and the tiles per range of every shape class the engine runs and of every forced variant."""
+    from pgmi import _native as N
+    lib = N.lib()
+    try:
+        for force, shape, ragged, ws, want in ATTN_PLANS:
+            assert lib.pgmi_tune_attention(force) == 0
+            out = [ctypes.c_int() for _ in range(4)]
+            assert lib.pgmi_debug_attention_plan(*shape, ragged, ws, *[ctypes.byref(o) for o in out]) == 0
+            assert tuple(o.value for o in out) == want, (force, shape, ragged, ws)
+    finally:
+        assert lib.pgmi_tune_attention(-1) == 0
+
+
+def test_tune_attention_takes_the_kept_variants_only():
+    """The id of the removed kernel (8, the 16-row kernel with its loads up front) and ids that never were one are
+    PGMI_E_ARG; the kept ones are taken."""
+    from pgmi import _native as N
+    lib = N.lib()
+    try:
+        for v in (8, 5, 80, 93):
+            assert lib.pgmi_tune_attention(v) == N.PGMI_E_ARG, v
+        for v in (0, 7, 41, 42, 21, 22, 44, 24, 9, 91, 92, 94, 81, 82, -1):
+            assert lib.pgmi_tune_attention(v) == 0, v
+    finally:
+        assert lib.pgmi_tune_attention(-1) == 0
+
+
 def test_create_validates_config_without_gpu():
     """pgmi_create only builds the weight layout (no device memory): it runs here."""
     from pgmi import _native as N

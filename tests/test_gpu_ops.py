@@ -243,7 +243,7 @@ def test_argmax_rows(eng, rows, V):
         assert torch.equal(got.cpu(), y[1:].view(rows, V).argmax(-1))
 
 
-@pytest.mark.parametrize("variant", [0, 7, 8, 41, 42, 21, 22, 44, 24, 9, 91, 92, 94, 81, 82])
+@pytest.mark.parametrize("variant", [0, 7, 41, 42, 21, 22, 44, 24, 9, 91, 92, 94, 81, 82])
 @pytest.mark.parametrize("B,Lq,Lk,H,Hkv,d,scale", [
     (1, 256, 256, 16, 16, 72, 72 ** -0.5),     # SigLIP 224
     (3, 17, 5, 16, 16, 72, 72 ** -0.5),        # fewer keys than one tile
@@ -258,7 +258,8 @@ def test_argmax_rows(eng, rows, V):
 ])
 def test_attention_forced_variant(eng, variant, B, Lq, Lk, H, Hkv, d, scale):
     """Every prefill attention kernel the tuning hook (pgmi_tune_attention) can force, against the
-    oracle restatement (variants a head dim does not have fall back to the default tiled kernel)."""
+    oracle restatement (7 or 82 on a shape they do not cover fall back to the measured choice for that shape,
+    the older families' variants to the default tiled kernel)."""
     from pgmi import _native as NN
     rng = np.random.default_rng(Lq * 3 + Lk + d + variant)
     q, k, v = rand(rng, B, Lq, H, d, scale=2.0), rand(rng, B, Lk, Hkv, d, scale=2.0), rand(rng, B, Lk, Hkv, d)
