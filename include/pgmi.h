@@ -396,6 +396,20 @@ int pgmi_decode_kernel(pgmi_ctx* ctx, int which, int layer, int B, void* stream)
  * [max_batch][hidden / 16], unstaged B >= 3 only), 7 = the step's next-id buffer (int64 [max_batch]).
  * Stream-ordered.  PGMI_E_ARG: a byte count outside the buffer. */
 int pgmi_debug_decode_buffer(pgmi_ctx* ctx, int which, void* buf, int64_t bytes, int write, void* stream);
+/* Test hook: copy `bytes` bytes between the flash-decoding partial records and the caller's device memory `buf`
+ * (write != 0: buf -> records), as pgmi_debug_decode_buffer does for the other buffers of the decode workspace.
+ * Stage 2's attention writes a record per live 64-key chunk and its o_proj combines them: fp32 [max_batch * kv heads]
+ * [(max_kv + 63) / 64 chunks][16 * 256 + 32] -- 16 head rows of 256, then 16 chunk maxima and 16 chunk sums.
+ * Stream-ordered.  PGMI_E_ARG: a byte count outside the buffer. */
+int pgmi_debug_decode_partials(pgmi_ctx* ctx, void* buf, int64_t bytes, int write, void* stream);
+/* Test hook: the kernels' in-register cross-lane reductions on their own.  in: device fp32 [rows][64]; one wave
+ * reduces each row (four rows per 256-thread workgroup) and writes EVERY lane's result to out, device fp32
+ * [rows][64].  op: 0 sum and 1 max over the xor butterfly o = 32, 16, .., 1; 2 first max, the pair (value, index)
+ * with a lane's index its lane number, larger value or lower index among equal values, same order; 3 sum over the
+ * 16 lanes of a row, o = 1, 2, 4, 8; 4 sum, o = 1, 2, .., 32; 5 sum, o = 16, 32; 6 first max and 7 max over 16
+ * lanes, o = 1, 2, 4, 8.  Ops 2 and 6 write the indices, int32 [rows][64], after the rows * 64 values (out holds
+ * 2 * rows * 64 words).  PGMI_E_ARG: an unknown op, rows < 1. */
+int pgmi_debug_lane_reduce(pgmi_ctx* ctx, int op, const float* in, int rows, float* out, void* stream);
 /* Test hook: run ONE stage of the decode step for batch B through the step's own launch code (the functions
  * pgmi_decode's body calls, with the same arguments), at the current pgmi_set_decode_staged_norm /
  * pgmi_set_decode_packed settings, on the decode workspace (pgmi_debug_decode_buffer):

@@ -104,9 +104,7 @@ __device__ __forceinline__ void attn_decode_block(const AttnArgs& a, const StepS
             m[rr] = sv[rr];
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) m[rr] = fmaxf(m[rr], __shfl_xor(m[rr], o, 64));
+        for (int rr = 0; rr < 4; ++rr) m[rr] = wave_max(m[rr]);  // o = 32 .. 1, in registers
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
             const int h = wave * 4 + rr;
@@ -116,9 +114,7 @@ __device__ __forceinline__ void attn_decode_block(const AttnArgs& a, const StepS
             l[rr] = e[rr];
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) l[rr] += __shfl_xor(l[rr], o, 64);
+        for (int rr = 0; rr < 4; ++rr) l[rr] = wave_sum(l[rr]);
         if (lane == 0) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {

@@ -122,6 +122,26 @@ int pgmi_debug_decode_buffer(pgmi_ctx* x, int which, void* buf, int64_t bytes, i
     return 0;
 }
 
+int pgmi_debug_decode_partials(pgmi_ctx* x, void* buf, int64_t bytes, int write, void* stream) {
+    int rc;
+    if (!x || !buf) return fail(PGMI_E_ARG, "null argument");
+    if ((rc = ensure_prepared(x))) return rc;
+    const int64_t cap = (int64_t)attention_decode_part_floats(x->c.max_batch, x->c.t_kv_heads, x->max_chunks) * 4;
+    if (bytes < 1 || bytes > cap) return fail(PGMI_E_ARG, "decode partials: byte count outside the buffer");
+    HIPCHK(hipMemcpyAsync(write ? (void*)x->opart : buf, write ? buf : (void*)x->opart, (size_t)bytes,
+                          hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+int pgmi_debug_lane_reduce(pgmi_ctx* x, int op, const float* in, int rows, float* out, void* stream) {
+    if (!x || !in || !out) return fail(PGMI_E_ARG, "null argument");
+    if (op < 0 || op >= kLaneReduceOps) return fail(PGMI_E_ARG, "lane reduce: unknown op");
+    if (rows < 1) return fail(PGMI_E_ARG, "lane reduce: no rows");
+    lane_reduce_rows((hipStream_t)stream, op, in, rows, out);
+    LAUNCHCHK();
+    return 0;
+}
+
 int pgmi_debug_prefill_stage(pgmi_ctx* x, int stage, int layer, int group, const int64_t* ids, const void* image_feats,
                              int n_img_rows, const void* embeds, int B, int L, const int64_t* positions,
                              const int32_t* lens, void* kv, int kv_batch, int kv_max, int kv_start, float* logits,

@@ -237,10 +237,12 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
                 f32x4 x0[CMAX], x1[CMAX];
                 float mc[CMAX], lc[CMAX];
                 // unconditional loads (chunk index clamped; records past nch are ignored below):
-                // a guarded load per chunk compiled to a branch and a wait per chunk
+                // a guarded load per chunk compiled to a branch and a wait per chunk.  The clamp is
+                // to the buffer's own chunk count, a kernel argument, so the loads do not wait for
+                // the step record that nch comes from; a stale record never enters arithmetic
 #pragma unroll
                 for (int c = 0; c < CMAX; ++c) {
-                    const long cs = (long)(c < nch ? c : nch - 1) * kAttnPartStride;
+                    const long cs = (long)(c < a.max_chunks ? c : a.max_chunks - 1) * kAttnPartStride;
                     x0[c] = ldxf4<false>(pb + cs);
                     x1[c] = ldxf4<false>(pb + cs + 4);
                     mc[c] = ldxf<false>(sp + cs);
@@ -598,12 +600,7 @@ __device__ __forceinline__ void gemv_block(const GemvArgs& a, const int blk, con
                         const int ix = ldi_coh(a.pidx + (long)b * nblk + i);
                         if (v > m || (v == m && ix < mi)) { m = v; mi = ix; }
                     }
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) {
-                        const float v = __shfl_xor(m, o);
-                        const int ix = __shfl_xor(mi, o);
-                        if (v > m || (v == m && ix < mi)) { m = v; mi = ix; }
-                    }
+                    wave_first_max(m, mi);
                     __syncthreads();  // bv/bi reuse across rows
                     if (lane == 0) { bv[wave][0] = m; bi[wave][0] = mi; }
                     __syncthreads();

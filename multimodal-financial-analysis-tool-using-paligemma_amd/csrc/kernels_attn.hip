@@ -403,16 +403,20 @@ __global__ void __launch_bounds__(64 * RG * KSPL) k_attn_fa(AttnArgs a) {
         }
     }
     // lanes g = 0..3 of a query, in a fixed order
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-        const float m2 = __shfl_xor(m, o, 64), l2 = __shfl_xor(l, o, 64);
-        if (lane & o) fa_comb(m, l, m2, l2);  // the higher lane group folds the lower one in ...
-        else {
-            float mm = m2, ll = l2;
-            fa_comb(mm, ll, m, l);            // ... the same way, so both sides agree bitwise
-            m = mm;
-            l = ll;
-        }
+    // (o = 16, then 32: both sides start from the higher lane group's pair and fold the lower one's
+    // in, so they agree bitwise; the swap leaves both pairs in every lane)
+    {
+        float mlo, mhi, llo, lhi;
+        lane_swap<16>(m, mlo, mhi);
+        lane_swap<16>(l, llo, lhi);
+        m = mhi;
+        l = lhi;
+        fa_comb(m, l, mlo, llo);
+        lane_swap<32>(m, mlo, mhi);
+        lane_swap<32>(l, llo, lhi);
+        m = mhi;
+        l = lhi;
+        fa_comb(m, l, mlo, llo);
     }
     if constexpr (KSPL > 1) {
         if (g == 0) {
@@ -565,8 +569,7 @@ __global__ void __launch_bounds__(256) k_attn_short(AttnArgs a) {
         }
     }
     // ---- exact softmax statistics: lane groups g, then the 4 waves in a fixed order
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    mx = red_asc<kRedMax, 32, 16>(mx);
     if (g == 0) red[0][wave][li] = mx;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's V DMAs landed (visible after the barrier)
     __syncthreads();
@@ -579,8 +582,7 @@ __global__ void __launch_bounds__(256) k_attn_short(AttnArgs a) {
             sc[t][r] = sc[t][r] == -INFINITY ? 0.f : fa_exp(sc[t][r] - M);
             sm += sc[t][r];
         }
-    sm += __shfl_xor(sm, 16, 64);
-    sm += __shfl_xor(sm, 32, 64);
+    sm = red_asc<kRedSum, 32, 16>(sm);
     if (g == 0) red[1][wave][li] = sm;
     __syncthreads();
     const float invl = 1.0f / (((red[1][0][li] + red[1][1][li]) + red[1][2][li]) + red[1][3][li]);
@@ -849,8 +851,7 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(FsArgs<CA> a, int
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int j = 0; j < 4; ++j) mx = fmaxf(mx, sv[kt][j]);
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        return fmaxf(mx, __shfl_xor(mx, 32, 64));
+        return red_asc<kRedMax, 32, 16>(mx);
     };
     // one tile ahead: iteration it multiplies K of tile it + 1 while it runs the softmax and P.V of
     // tile it (the two are independent, so the MFMAs of one overlap the VALU of the other)
@@ -907,8 +908,7 @@ __global__ void __launch_bounds__(64 * (NW + LW), 1) k_attn_fs(FsArgs<CA> a, int
         slot = nslot;
     }
     // row sums: the 4 lane groups of query li, in a fixed order
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
+    l = red_asc<kRedSum, 32, 16>(l);
     if (ns == 1) {
         const float inv = 1.0f / l;
         uint16_t* orow[4];

@@ -284,14 +284,12 @@ __device__ __forceinline__ void lse_wave(const EpiArgs& ea, int M, int N, int mb
                 mx = fmaxf(mx, x[j]);
                 if (n == lb[i][r] && m < M) ea.lse_lab[m] = v;  // lb < N: the column is a real one
             }
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+            mx = row16_max_asc(mx);
             const float ms = mx == -INFINITY ? 0.f : mx;  // a wave whose columns are all past N: s = 0
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < TN; ++j) s += expf(x[j] - ms);
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
+            s = row16_sum_asc(s);
             if ((lane & 15) == 0) sm[wn * BM + rl0 + i * 16 + (lane >> 4) * 4 + r] = make_float2(mx, s);
         }
 }

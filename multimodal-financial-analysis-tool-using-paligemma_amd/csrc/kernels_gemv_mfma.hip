@@ -351,8 +351,7 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
         float ss = 0.f;
 #pragma unroll
         for (int c = 0; c < (FOLD ? Q4 / 4 : 1); ++c) { ss += sv[c][0]; ss += sv[c][1]; ss += sv[c][2]; ss += sv[c][3]; }
-        ss += __shfl_xor(ss, 16, 64);
-        ss += __shfl_xor(ss, 32, 64);
+        ss = red_asc<kRedSum, 32, 16>(ss);
         const float r = 1.0f / sqrtf(ss / (float)KF + a.eps);
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
@@ -432,7 +431,7 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
             // the rotary partner of this lane's row is lane n ^ 8's (same rows b)
             f32x4 part;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) part[r] = __shfl_xor(acc[0][r], 8, 64);
+            for (int r = 0; r < 4; ++r) part[r] = lane_xor<8>(acc[0][r]);
             const int hh = cur >> 4, d = (cur & 15) * 8 + (n & 7), hi = n >> 3;
             const int nh = a.I;
 #pragma unroll
@@ -480,8 +479,7 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
                 if (a.ssq) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                        for (int o = 1; o < 16; o <<= 1) q[r] += __shfl_xor(q[r], o, 64);
+                        q[r] = row16_sum_asc(q[r]);
                         if (n == 0 && 4 * g + r < a.nb) a.ssq[(long)(4 * g + r) * n_groups + cur] = q[r];
                     }
                 }
@@ -517,12 +515,7 @@ __global__ void __launch_bounds__(64 * WK) k_gemv_mf(GemvArgs a, float* __restri
             for (int r = 0; r < 4; ++r) {
                 float m = best[r];
                 int mi = besti[r];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) {
-                    const float m2 = __shfl_xor(m, o, 64);
-                    const int i2 = __shfl_xor(mi, o, 64);
-                    if (m2 > m || (m2 == m && i2 < mi)) { m = m2; mi = i2; }
-                }
+                row16_first_max_asc(m, mi);
                 if (n == 0) { bv[4 * g + r] = m; bi[4 * g + r] = mi; }
             }
         }
@@ -730,12 +723,7 @@ __global__ void __launch_bounds__(256, 1) k_gemv_ml(GemvArgs a, float* __restric
         for (int r = 0; r < 4; ++r) {
             float m = best[r];
             int mi = besti[r];
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                const float m2 = __shfl_xor(m, o, 64);
-                const int i2 = __shfl_xor(mi, o, 64);
-                if (m2 > m || (m2 == m && i2 < mi)) { m = m2; mi = i2; }
-            }
+            row16_first_max_asc(m, mi);
             if (n == 0) { bv[wave][4 * g + r] = m; bi[wave][4 * g + r] = mi; }
         }
         __syncthreads();

@@ -633,11 +633,7 @@ __global__ void k_argmax_part(const float* __restrict__ x, int V, int slice, flo
     } else {
         for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) amax_take(xr[i], i, best, bi);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v = __shfl_xor(best, o, 64);
-        const int ix = __shfl_xor(bi, o, 64);
-        amax_take(v, ix, best, bi);
-    }
+    wave_first_max(best, bi);  // amax_take's rule, o = 32 .. 1
     __shared__ float sv[4];
     __shared__ int si[4];
     if ((threadIdx.x & 63) == 0) {
@@ -657,6 +653,32 @@ __global__ void k_argmax_part(const float* __restrict__ x, int V, int slice, flo
 }
 
 int argmax_scratch_parts() { return 1024; }
+
+// ---------------------------------------------------------------- the in-register reductions, on their own (tests)
+__global__ void __launch_bounds__(256) k_lane_reduce(int op, const float* __restrict__ in, int rows,
+                                                     float* __restrict__ out) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;  // (a whole wave)
+    float v = in[(long)row * 64 + lane];
+    int ix = lane;
+    switch (op) {
+        case kLaneSum: v = wave_sum(v); break;
+        case kLaneMax: v = wave_max(v); break;
+        case kLaneFirstMax: wave_first_max(v, ix); break;
+        case kLaneRow16Sum: v = row16_sum_asc(v); break;
+        case kLaneSumAsc: v = red_asc<kRedSum, 32>(v); break;
+        case kLaneQuarterSum: v = red_asc<kRedSum, 32, 16>(v); break;
+        case kLaneRow16FirstMax: row16_first_max_asc(v, ix); break;
+        default: v = row16_max_asc(v); break;
+    }
+    out[(long)row * 64 + lane] = v;
+    if (op == kLaneFirstMax || op == kLaneRow16FirstMax)
+        reinterpret_cast<int*>(out)[((long)rows + row) * 64 + lane] = ix;
+}
+
+void lane_reduce_rows(hipStream_t s, int op, const float* in, int rows, float* out) {
+    hipLaunchKernelGGL(k_lane_reduce, dim3((rows + 3) / 4), dim3(256), 0, s, op, in, rows, out);
+}
 
 void argmax_rows(hipStream_t s, const float* x, int rows, int V, float* pmax, int* pidx, int64_t* out) {
     int nb = rows >= argmax_scratch_parts() ? 1 : argmax_scratch_parts() / rows;
@@ -680,7 +702,7 @@ __global__ void __launch_bounds__(256) k_logprob_part(const float* __restrict__ 
     __shared__ float sv[4];
     float mx = -INFINITY;
     for (int i = lo + tid; i < hi; i += 256) mx = fmaxf(mx, xr[i]);
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mx = wave_max(mx);
     if ((tid & 63) == 0) sv[tid >> 6] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
@@ -688,7 +710,7 @@ __global__ void __launch_bounds__(256) k_logprob_part(const float* __restrict__ 
     const float ms = mx == -INFINITY ? 0.f : mx;
     float s = 0.f;
     for (int i = lo + tid; i < hi; i += 256) s += expf(xr[i] - ms);
-    for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+    s = red_asc<kRedSum, 32>(s);  // o = 1, 2, .., 32
     if ((tid & 63) == 0) sv[tid >> 6] = s;
     __syncthreads();
     if (tid == 0) {

@@ -175,6 +175,21 @@ void argmax_finish(hipStream_t s, int B, const float* pmax, const int* pidx, int
                    StepState* adv = nullptr, int64_t* hist = nullptr, int adv_n = 1);
 int argmax_scratch_parts();
 void argmax_rows(hipStream_t s, const float* x, int rows, int V, float* pmax, int* pidx, int64_t* out);
+// common.h's in-register reductions on rows of 64 fp32 values, one wave per row and four rows per workgroup; every
+// lane's result is written: out[row][lane] (ops kLaneFirstMax / kLaneRow16FirstMax: the indices, int32
+// [rows][64], follow the rows * 64 values; a lane's starting index is its lane number)
+enum LaneReduceOp {
+    kLaneSum = 0,            // wave_sum: o = 32, 16, .., 1
+    kLaneMax = 1,            // wave_max
+    kLaneFirstMax = 2,       // wave_first_max
+    kLaneRow16Sum = 3,       // row16_sum_asc: o = 1, 2, 4, 8
+    kLaneSumAsc = 4,         // o = 1, 2, .., 32
+    kLaneQuarterSum = 5,     // o = 16, 32
+    kLaneRow16FirstMax = 6,  // row16_first_max_asc
+    kLaneRow16Max = 7,       // row16_max_asc
+    kLaneReduceOps = 8
+};
+void lane_reduce_rows(hipStream_t s, int op, const float* in, int rows, float* out);
 // lse[row] (may be null) = logsumexp(x[row]) and logprob[row] = x[row][ids[row]] - lse[row] over fp32 rows
 // [rows][V] (0 for ids[row] == ignore_index, NaN for any other id outside [0, V)); pm / ps: scratch of
 // argmax_scratch_parts() floats each

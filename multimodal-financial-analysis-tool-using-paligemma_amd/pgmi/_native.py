@@ -123,6 +123,8 @@ SIGNATURES = {
     "pgmi_eos_update": (i32, [vp, vp, vp, i32, i64, i64, vp, vp]),
     "pgmi_decode_kernel": (i32, [vp, i32, i32, i32, vp]),
     "pgmi_debug_decode_buffer": (i32, [vp, i32, vp, i64, i32, vp]),
+    "pgmi_debug_decode_partials": (i32, [vp, vp, i64, i32, vp]),
+    "pgmi_debug_lane_reduce": (i32, [vp, i32, vp, i32, vp, vp]),
     "pgmi_debug_decode_stage": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp]),
     "pgmi_debug_prefill_buffer": (i32, [vp, i32, vp, i64, i32, vp]),
     "pgmi_debug_prefill_stage": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32,

@@ -777,6 +777,29 @@ class Engine:
                                                  int(bool(ragged)), N.ptr(mask), mdt, self._s()),
                 "pgmi_debug_decode_stage")
 
+    def decode_partials(self, t: torch.Tensor, write: bool = False) -> torch.Tensor:
+        """Copy the flash-decoding partial records between the decode attention and o_proj (fp32 [max_batch * kv
+        heads][chunks][16 * 256 + 32]) into the contiguous device tensor t, or (write) t into them
+        (pgmi_debug_decode_partials: a test hook)."""
+        self._ready()
+        if t.device != self.device or not t.is_contiguous():
+            raise ValueError("decode_partials: a contiguous tensor on the engine's device")
+        N.check(self.lib.pgmi_debug_decode_partials(self.ctx, t.data_ptr(), t.numel() * t.element_size(),
+                                                    int(bool(write)), self._s()), "pgmi_debug_decode_partials")
+        return t
+
+    def lane_reduce(self, op: int, rows: torch.Tensor):
+        """The kernels' in-register cross-lane reductions on fp32 rows of 64 (pgmi_debug_lane_reduce: a test hook):
+        every lane's result, fp32 [rows][64]; ops 2 and 6 (first max) return (values, int32 indices)."""
+        if rows.dtype is not torch.float32 or rows.device != self.device or not rows.is_contiguous() or \
+                rows.dim() != 2 or rows.shape[1] != 64:
+            raise ValueError("lane_reduce: a contiguous fp32 [rows][64] tensor on the engine's device")
+        pair = int(op) in (2, 6)
+        out = torch.empty((2 if pair else 1, rows.shape[0], 64), dtype=torch.float32, device=self.device)
+        N.check(self.lib.pgmi_debug_lane_reduce(self.ctx, int(op), rows.data_ptr(), rows.shape[0], out.data_ptr(),
+                                                self._s()), "pgmi_debug_lane_reduce")
+        return (out[0], out[1].view(torch.int32)) if pair else out[0]
+
     def decode_buffer(self, which: int, t: torch.Tensor, write: bool = False) -> torch.Tensor:
         """Copy the decode workspace's h (0) / act (1) / logits (2) / q (3) / attention output (4, B >= 3) / hn (5) /
         ssq (6) / next ids (7) rows into the contiguous device tensor t, or (write) t into the workspace
